@@ -126,6 +126,25 @@ def build_inputs(batch, device, seed=1234):
     return preprocess_device(torch.from_numpy(imgs).to(device))               # [B,3,420,620] fp32, log domain (harness.hip)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (the codebook indices are exact in it).  Past DUMP_LIMIT_BYTES in all,
+    each array is cut by the same fraction to a sample at flat positions drawn from a fixed seed, so two runs at the same arguments
+    write the same elements."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def build_nets(device):
     from glare_amd import modules as M
     from glare_amd.synthetic import seeded_init_
@@ -524,7 +543,13 @@ def main():
                                                                   "warm-up gathers, barriers, timed region, MAX all-reduce) may take before rank 0 "
                                                                   "prints the line with `config.exchange.error` and the job ends")
     ap.add_argument("--breakdown", action="store_true", help="per-stage timing on stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, rank 0 writes what the LAST timed step computed -- the enhanced images, the latent and "
+                         "the codebook indices -- as DIR/<name>.npy (float32, at most 64 MB in all); the inputs and weights are seeded, so "
+                         "two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as a plain process (`python bench.py --gpus N`): start the N ranks ourselves, one per GPU over RCCL;
@@ -616,11 +641,13 @@ def main():
         gatherers = [parallel.RankGather(torch.empty(shape, dtype=torch.uint8, device=device), rank, world) for _ in range(max(1, args.streams))]
 
     GATHER_EVENTS = None
+    LAST = {}                                                       # what the latest step returned (--dump-outputs)
 
     def enhance(slot=0):
         gatherer = gatherers[slot] if gatherers is not None else None
         if STUB:
             out = lr * 2.0                                          # stands in for the HIP pipeline
+            LAST["out"] = out
             if gatherer is not None and rank == 1 and os.environ.get("GLARE_BENCH_STUB_HANG_GATHER") == "1":
                 time.sleep(3600)                                    # tests: a rank that never reaches the step's gather
             if gatherer is not None:
@@ -628,7 +655,9 @@ def main():
                 if rank == 0:
                     assert [int(b[0, 0, 0, 0]) for b in bufs] == [2 * (r + 1) for r in range(world)]   # every rank's batch arrived
             return out
-        out = netG.reverse_flow_nhwc(net_vq, lr)["out"]
+        r = netG.reverse_flow_nhwc(net_vq, lr)
+        out = r["out"]
+        LAST.update(out=out, latent=r["latent"], indices=r["indices"])
         if gatherer is not None:
             restored, _ = harness.postprocess_device(out, H_IMG, W_IMG)
             u8 = harness.to_ubyte_device(restored)                  # img_as_ubyte: 5.8 MB per rank and step instead of 23 MB
@@ -667,6 +696,8 @@ def main():
         live_events, ops.ATTENTION_LAUNCH_EVENTS = ops.ATTENTION_LAUNCH_EVENTS or [], None
         family_events, ops.LAUNCH_EVENTS = ops.LAUNCH_EVENTS or {}, None
         gather_events, GATHER_EVENTS = GATHER_EVENTS or [], None
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, LAST)             # before any later step replaces them
     assert bool(torch.isfinite(out).all())
     if dog is not None:
         dog.stage("MAX all-reduce of the step time + all-gather of the per-rank times")
@@ -704,7 +735,7 @@ def main():
         total_images = args.batch * world * args.steps
         res = {
             "metric": "enhanced images/sec (400x600)", "value": round(total_images / dt, 3), "unit": "images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 6),
             "higher_is_better": True, "scaling": "strong" if args.global_batch is not None else "weak", "vs_baseline": None,
             "dtype": args.precision, "data": "synthetic",
             "config": {"workload": ("LOL-v2-real-shaped 400x600 inference, global batch=%d split over %d GPU(s) = %d per GPU, full "

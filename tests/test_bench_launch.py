@@ -25,6 +25,7 @@ def test_launch_ranks_starts_world_size_processes(tmp_path):
         sys.path.insert(0, %r)
         import torch, torch.distributed as dist
         from glare_amd import parallel
+        torch.cuda.is_available = lambda: False     # the gloo branch of init_from_env, also where fewer GPUs than ranks are visible
         rank, world, dev = parallel.init_from_env(backend="gloo")
         t = torch.tensor([float(rank + 1)])
         dist.all_reduce(t)
@@ -138,3 +139,35 @@ def test_bench_prints_its_line_when_the_first_gather_hangs():
     assert res["stub"] is True and res["n_gpus"] == 2 and res["value"] is None
     err = res["config"]["exchange"]["error"]
     assert "did not finish within 8 s" in err and ("first step" in err or "gather" in err)
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: after the timed region rank 0 writes what the last timed step returned as DIR/<name>.npy in float32 (the
+    stub's step returns 2 x its constant input), and --steps sets the number of timed steps the line reports."""
+    import numpy as np
+
+    r, lines = _run_bench_stub(["--steps", "3", "--warmup", "1", "--batch", "2", "--no-train", "--dump-outputs", str(tmp_path / "d")],
+                               timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(lines) == 1 and lines[0]["steps"] == 3 and lines[0]["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "d")) == ["out.npy"]
+    out = np.load(tmp_path / "d" / "out.npy")
+    assert out.dtype == np.float32 and out.shape == (2, 3, 8, 12) and (out == 2.0).all()
+
+
+def test_bench_dump_outputs_samples_past_the_limit(tmp_path, monkeypatch):
+    """Past the byte budget every array is cut by the same fraction to a sample drawn from a fixed seed: two dumps agree."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    arrays = {"a": torch.arange(1000, dtype=torch.float64), "b": torch.arange(2000, dtype=torch.int64)}
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a, b = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "x" / "b.npy")
+    assert a.dtype == b.dtype == np.float32 and a.nbytes + b.nbytes <= 4000 and a.size == 333 and b.size == 666
+    assert (np.diff(a) > 0).all() and (np.diff(b) > 0).all() and set(a) <= set(range(1000))
+    assert (np.load(tmp_path / "y" / "a.npy") == a).all() and (np.load(tmp_path / "y" / "b.npy") == b).all()

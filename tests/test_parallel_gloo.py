@@ -18,9 +18,16 @@ def test_shard_range_covers_everything():
             assert max(sizes) - min(sizes) <= 1
 
 
+def _host_only():
+    """The workers run the CPU (gloo) branch of init_from_env wherever they start: with a GPU visible it would bind rank r to cuda:r,
+    which a machine with fewer GPUs than ranks does not have."""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, n_items, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    _host_only()
     r, w, dev = parallel.init_from_env(backend="gloo")
     data = torch.arange(n_items, dtype=torch.float32).view(n_items, 1, 1).expand(n_items, 2, 3).contiguous()
 
@@ -61,6 +68,7 @@ def _grad_worker(rank, world, port, q):
 
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    _host_only()
     parallel.init_from_env(backend="gloo")
     torch.manual_seed(0)
     net = torch.nn.Sequential(torch.nn.Linear(5, 4), torch.nn.Linear(4, 3))
@@ -105,6 +113,7 @@ def _branch_worker(rank, world, port, q):
 
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    _host_only()
     parallel.init_from_env(backend="gloo")
     torch.manual_seed(0)
     net = torch.nn.Sequential(torch.nn.Linear(5, 4), torch.nn.Linear(4, 3))
@@ -164,6 +173,7 @@ def _early_worker(rank, world, port, q):
 
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
+    _host_only()
     parallel.init_from_env(backend="gloo")
     torch.manual_seed(0)
     early_layers, late_layers = torch.nn.Linear(5, 4), torch.nn.Linear(4, 3)       # "encoder" in front of the "flow"
