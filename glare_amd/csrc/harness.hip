@@ -118,6 +118,91 @@ __global__ __launch_bounds__(256) void ubyte_planes_kernel(const float* __restri
   y255[i] = (float)gt[i];
 }
 
+
+// ---- unpaired harness (code/infer_unpaired.py:81-136): any size, borders on all four sides, uint8 out --------------------
+// cv2.borderInterpolate: REFLECT101 (numpy 'reflect', gfedcb|abcdefgh|gfedcba) folds with period 2n - 2, REFLECT (numpy
+// 'symmetric', cv2.BORDER_REFLECT, fedcba|abcdefgh|hgfedcb) with period 2n; a side of one pixel maps every index to 0
+__device__ __forceinline__ int fold_index(long long i, int n, int mode) {
+  if (n == 1) return 0;
+  if (mode == GLARE_PAD_SYMMETRIC) {
+    const long long per = 2LL * n;
+    long long p = i % per;
+    if (p < 0) p += per;
+    return (int)(p < n ? p : per - 1 - p);
+  }
+  const long long per = 2LL * n - 2;
+  long long p = i % per;
+  if (p < 0) p += per;
+  return (int)(p < n ? p : per - p);
+}
+
+// uint8 HWC [B][H][W][3] -> fp32 NCHW [B][3][Hp][Wp], one thread per output value (coalesced fp32 stores)
+__global__ __launch_bounds__(256) void pre_pad_kernel(const uint8_t* __restrict__ img, int B, int H, int W, int top, int left, int Hp,
+                                                      int Wp, int mode, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long plane = (long long)Hp * Wp;
+  if (i >= (long long)B * 3 * plane) return;
+  const long long bc = i / plane, r = i - bc * plane;
+  const int y = (int)(r / Wp), x = (int)(r - (long long)y * Wp);
+  const int b = (int)(bc / 3), c = (int)(bc - 3LL * b);
+  const int ys = fold_index((long long)y - top, H, mode), xs = fold_index((long long)x - left, W, mode);
+  const float v = (float)img[(((long long)b * H + ys) * W + xs) * 3 + c];
+  out[i] = logf(fmaxf(__fdiv_rn(v, 255.f) + 1e-3f, 1e-3f));
+}
+
+constexpr int HBU = 128;  // blocks per image of the uint8 post-process (two int partials each: < glare_harness_postprocess_workspace_bytes)
+
+// fp32 NCHW [B][3][Hp][Wp] -> uint8 HWC [B][h][w][3] of the window at (top, left): (uint8)(clamp(x, 0, 1) * 255), truncating
+// (rgb(), infer_unpaired.py:42).  The output is one flat byte array; each thread writes one aligned 4-byte word of it.  A word
+// belongs to the image of its first byte, so the last word of an image can carry the first bytes of the next one: their
+// non-finite values go to a second partial (`spill`), and the per-image count stays a deterministic two-level integer sum.
+__global__ __launch_bounds__(256) void post_u8_kernel(const float* __restrict__ out, int B, int Hp, int Wp, int top, int left, int h, int w,
+                                                      uint8_t* __restrict__ dst, int* __restrict__ bad_partial) {
+  __shared__ int red[2][4];
+  const int b = blockIdx.y;
+  const long long n = 3LL * h * w, total = n * B;
+  const long long wlo = (n * b + 3) / 4, whi = (n * (b + 1) + 3) / 4;    // words whose first byte lies in image b
+  int bad_own = 0, bad_next = 0;
+  for (long long wd = wlo + (long long)blockIdx.x * 256 + threadIdx.x; wd < whi; wd += (long long)HBU * 256) {
+    const long long k0 = wd * 4;
+    int bk = b;
+    long long r = k0 - n * b;
+    const long long p = r / 3;
+    int c = (int)(r - 3 * p);
+    int y = (int)(p / w), x = (int)(p - (long long)y * w);
+    uint32_t word = 0;
+    const int nb = total - k0 < 4 ? (int)(total - k0) : 4;
+    for (int j = 0; j < nb; ++j) {
+      const float v = out[(((long long)bk * 3 + c) * Hp + top + y) * Wp + left + x];
+      const int nf = (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;   // inf or NaN, counted BEFORE the clamp
+      if (bk == b) bad_own += nf; else bad_next += nf;
+      word |= (uint32_t)(uint8_t)(fminf(fmaxf(v, 0.f), 1.f) * 255.f) << (8 * j);
+      if (++c == 3) { c = 0; if (++x == w) { x = 0; if (++y == h) { y = 0; ++bk; } } }
+    }
+    if (nb == 4) {
+      *reinterpret_cast<uint32_t*>(dst + k0) = word;
+    } else {
+      for (int j = 0; j < nb; ++j) dst[k0 + j] = (uint8_t)(word >> (8 * j));
+    }
+  }
+  if (!bad_partial) return;
+  for (int o = 32; o > 0; o >>= 1) { bad_own += __shfl_xor(bad_own, o, 64); bad_next += __shfl_xor(bad_next, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = bad_own; red[1][threadIdx.x >> 6] = bad_next; }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    bad_partial[((size_t)threadIdx.x * B + b) * HBU + blockIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+__global__ void post_u8_count_kernel(const int* __restrict__ bad_partial, int B, int* __restrict__ nonfinite) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int s = 0;
+  for (int k = 0; k < HBU; ++k) s += bad_partial[(size_t)b * HBU + k];                                  // own words
+  if (b > 0)
+    for (int k = 0; k < HBU; ++k) s += bad_partial[((size_t)B + b - 1) * HBU + k];                      // the previous image's last word
+  nonfinite[b] = s;
+}
+
 }  // namespace
 
 // restored float in [0,1] -> uint8 = rint(clip * 255): img_as_ubyte(restored), the image the reference's loop hands to imwrite
@@ -176,4 +261,35 @@ extern "C" int glare_harness_postprocess_f32(const float* out_nchw, const unsign
                                              size_t workspace_bytes, glare_stream_t stream) {
   return glare_harness_postprocess_flagged_f32(out_nchw, gt_hwc_or_null, B, h, w, Hp, Wp, pad, restored_hwc, psnr_or_null, nullptr, workspace,
                                                workspace_bytes, stream);
+}
+
+extern "C" int glare_harness_preprocess_pad_u8(const unsigned char* img_hwc, int B, int H, int W, int top, int bottom, int left, int right,
+                                               int mode, float* out_nchw, glare_stream_t stream) {
+  if (!img_hwc || !out_nchw || B <= 0 || H <= 0 || W <= 0 || top < 0 || bottom < 0 || left < 0 || right < 0) return GLARE_ERR_INVALID;
+  if (mode != GLARE_PAD_REFLECT101 && mode != GLARE_PAD_SYMMETRIC) return GLARE_ERR_INVALID;
+  const long long Hp = (long long)H + top + bottom, Wp = (long long)W + left + right;
+  if (Hp > 0x7fffffffLL || Wp > 0x7fffffffLL) return GLARE_ERR_INVALID;
+  const long long blocks = cdivll((long long)B * 3 * Hp * Wp, 256);
+  if (blocks > 0x7fffffffLL) return GLARE_ERR_INVALID;
+  hipLaunchKernelGGL(pre_pad_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), img_hwc, B, H, W, top, left,
+                     (int)Hp, (int)Wp, mode, out_nchw);
+  return glare_launch_status();
+}
+
+extern "C" int glare_harness_postprocess_u8(const float* out_nchw, int B, int Hp, int Wp, int top, int left, int h, int w,
+                                            unsigned char* out_hwc_u8, int* nonfinite_or_null, void* workspace, size_t workspace_bytes,
+                                            glare_stream_t stream) {
+  if (!out_nchw || !out_hwc_u8 || B <= 0 || h <= 0 || w <= 0 || top < 0 || left < 0) return GLARE_ERR_INVALID;
+  if ((long long)top + h > Hp || (long long)left + w > Wp) return GLARE_ERR_INVALID;
+  if (B > 65535 || 3LL * h * w > 0x7fffffffLL) return GLARE_ERR_INVALID;     // grid.y = B; one image's bytes, a word offset of 32 bits
+  int* bad_partial = nullptr;
+  if (nonfinite_or_null) {
+    static_assert(HBU * 2 * sizeof(int) <= HB * (3 * sizeof(double) + sizeof(int)), "the partials fit the documented workspace");
+    if (!workspace || workspace_bytes < glare_harness_postprocess_workspace_bytes(B)) return GLARE_ERR_WORKSPACE;
+    bad_partial = static_cast<int*>(workspace);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(post_u8_kernel, dim3(HBU, B), dim3(256), 0, s, out_nchw, B, Hp, Wp, top, left, h, w, out_hwc_u8, bad_partial);
+  if (nonfinite_or_null) hipLaunchKernelGGL(post_u8_count_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, bad_partial, B, nonfinite_or_null);
+  return glare_launch_status();
 }

@@ -1,0 +1,277 @@
+"""Unpaired enhancement: photos of any size, no ground truth, enhanced images written back out -- the GLARE counterpart of
+code/infer_unpaired.py:91-136 on the HIP path.
+
+    python -m glare_amd.enhance photos/ more/img.png --out enhanced/ [--net-g G.pth --net-vq VQ.pth --precision fp16 --batch 8]
+
+Per image, the reference's steps: read as RGB uint8 (cv2.imread, :47), auto_padding to a multiple of 16 with cv2.BORDER_REFLECT
+(:81-88), /255, log(clamp(x + 1e-3, min=1e-3)) (:39, :122), the network (get_sr, :128), crop + clamp + rgb() -- which truncates
+(:42, :129-130) -- and imwrite under the same basename (:136).  Padding, the log transform, the crop and the uint8 conversion run on
+the device (csrc/harness.hip): images cross PCIe as uint8 both ways.  Images of one padded shape are enhanced in batches; the size
+envelope of the kernels (SIZE_TABLE) is checked before anything is launched.  Without checkpoints the weights are name-seeded."""
+import argparse
+import glob
+import json
+import os
+import re
+import time
+
+import numpy as np
+
+from . import harness
+
+# ---- the size envelope ------------------------------------------------------------------------------------------------------
+# Extents of the inference graph that the kernels address through 32-bit buffer offsets or 31-bit block counts, in bytes (or
+# blocks) per PADDED full-resolution pixel.  Every row names the C check it mirrors; the product returns GLARE_ERR_UNSUPPORTED /
+# GLARE_ERR_INVALID (or, for the DCN, leaves its fast path) above the limit.  An extent is
+#     ceil64(Hp * Wp) * (per_image + per_more_image * (B - 1)) + const
+# (ceil64: the DCN's offset planes are padded to 64 pixels; applied to every row, so each is an upper bound).  Derived from the layer
+# list (ch = 128, ch_mult = (1, 2, 4), attention at 1/4 resolution with 512 channels, WarpBlock DCN: dg = 4, 3 x 3) and checked
+# against every launch of a run by tests/test_gpu_enhance.py.
+# (name, C check, per_image, per_more_image, const, limit; an extent must stay < limit)
+SIZE_TABLE = (
+    # the two decoders' first ResnetBlock at full resolution reads the upsampled 256-channel map: 256 ch x 2 B
+    ("conv source, one image", "conv_igemm.hip:392-394  H*W*pitch*2 < 0x7ff00000", 512, 0, 0, 0x7ff00000),
+    # the full-resolution WarpBlock: x = the VQ decoder's 128-channel feature, 16-bit, the whole batch
+    ("DCN x, whole batch", "dcn.hip:771-781  B*H*W*pitch*2 < 2^31-1", 256, 256, 0, 0x7fffffff),
+    # conv_offset's planar fp32 output [B][3*dg*9 = 108][plane]: the offsets are its first 72 planes, the mask the last 36
+    ("DCN offsets, whole batch", "dcn.hip:773-781  ((B-1)*108 + 72)*plane*4 < 2^31-1", 288, 432, 0, 0x7fffffff),
+    ("DCN mask, whole batch", "dcn.hip:774-781  ((B-1)*108 + 36)*plane*4 < 2^31-1", 144, 432, 0, 0x7fffffff),
+    # attention at 1/4 resolution (N = Hp*Wp/16 tokens): q and k interleaved, ldk = 1024 (AttnBlock's d512 form), 16-bit
+    ("attention K, one image", "attn.hip:712  (N*ldk + 512)*2 < 0x7ff00000", 128, 0, 1024, 0x7ff00000),
+    ("attention V^T, one image", "attn.hip:712  512*v_pitch*2 < 0x7ff00000", 64, 0, 65536, 0x7ff00000),
+    ("attention K/V (shared), one image", "attn.hip:674  (N*ldkv + 512)*2 < 0x7ff00000", 64, 0, 1024, 0x7ff00000),
+    ("conv1x1 pixels, one image", "conv1x1.hip:403/466  pixels_per_image <= 2^31-1", 1, 0, 0, 0x80000000),
+)
+
+
+def _extent(row, hp, wp, batch):
+    _, _, per, more, const, _ = row
+    px = (hp * wp + 63) // 64 * 64
+    return px * (per + more * (batch - 1)) + const
+
+
+def check_size(hp, wp, batch=1, name=None):
+    """Raises ValueError, before any launch, when a batch of `batch` images padded to hp x wp crosses a row of SIZE_TABLE."""
+    for row in SIZE_TABLE:
+        e = _extent(row, hp, wp, batch)
+        if e >= row[5]:
+            raise ValueError("%s: padded size %dx%d (batch %d) is outside the size envelope: %s = %d B, limit %d B (%s)"
+                             % (name or "image", hp, wp, batch, row[0], e, row[5], row[1]))
+
+
+def max_batch(hp, wp, cap=1 << 16):
+    """The largest batch of hp x wp padded images that check_size accepts (0: not even one)."""
+    b = 0
+    while b < cap:
+        try:
+            check_size(hp, wp, b + 1)
+        except ValueError:
+            break
+        b += 1
+    return b
+
+
+# ---- reading and writing ----------------------------------------------------------------------------------------------------
+def natural_key(path):
+    """natsort's order for plain file names: digit runs compare as numbers (img2 before img10)."""
+    return [(0, int(t), "") if t.isdigit() else (1, 0, t) for t in re.split(r"(\d+)", os.path.basename(path)) if t != ""]
+
+
+def list_inputs(paths):
+    """Files and folders -> file list; a folder means <dir>/*.* in natural order (fiFindByWildcard, infer_unpaired.py:17-18)."""
+    out = []
+    for p in paths:
+        if os.path.isdir(p):
+            out += sorted((f for f in glob.glob(os.path.join(p, "*.*")) if os.path.isfile(f)), key=natural_key)
+        else:
+            out.append(p)
+    return out
+
+
+# PIL modes cv2.imread(IMREAD_COLOR) turns into 8-bit BGR that PIL converts to RGB the same way: 8-bit gray (+ alpha), palette, colour
+_CONVERTIBLE = {"RGB", "RGBA", "RGBX", "L", "LA", "P", "PA", "1", "CMYK", "YCbCr"}
+
+
+def read_image(path):
+    """-> (uint8 [H,W,3] RGB, None) or (None, reason).  EXIF orientation applied (cv2's IMREAD_COLOR does), gray -> 3 channels,
+    alpha dropped; modes that do not convert to 8-bit RGB faithfully (16-bit, float) are refused."""
+    from PIL import Image, ImageOps
+
+    try:
+        with Image.open(path) as im:
+            im.load()
+            mode = im.mode
+            if mode not in _CONVERTIBLE:
+                return None, "unsupported image mode %s" % mode
+            im = ImageOps.exif_transpose(im)
+            if mode in ("RGBA", "LA", "PA") or (mode == "P" and "transparency" in im.info):
+                im = im.convert("RGBA").convert("RGB")      # alpha dropped, not composited (cv2.imread's IMREAD_COLOR)
+            else:
+                im = im.convert("RGB")
+            return np.ascontiguousarray(np.asarray(im, dtype=np.uint8)), None
+    except Exception as e:          # not an image, truncated, unknown format
+        return None, "cannot read: %s" % (str(e) or type(e).__name__)
+
+
+def write_image(path, img):
+    from PIL import Image
+
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    ext = os.path.splitext(path)[1].lower()
+    kw = {"quality": 95} if ext in (".jpg", ".jpeg") else {}        # cv2.IMWRITE_JPEG_QUALITY defaults to 95
+    Image.fromarray(img).save(path, **kw)
+
+
+# ---- the network call -------------------------------------------------------------------------------------------------------
+def device_enhance_fn(netG, net_vq, device):
+    """enhance_fn over the HIP path: pinned uint8 [n,H,W,3] + pads -> (uint8 [n,h,w,3] on the host, int32 [n] non-finite counts).
+    The uint8 batch crosses PCIe as uint8; pad, log, network, crop and rgb() run on the device."""
+    import torch
+
+    def fn(batch_u8, pads, precision):
+        h, w = batch_u8.shape[1], batch_u8.shape[2]
+        src = batch_u8 if isinstance(batch_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(batch_u8))
+        lr = harness.preprocess_unpaired_device(src.to(device, non_blocking=True), pads)
+        with torch.no_grad():
+            out = netG.reverse_flow_nhwc(net_vq, lr, precision=precision)["out"]
+        u8, bad = harness.postprocess_unpaired_device(out, pads, h, w, want_nonfinite=True)
+        return u8.cpu().numpy(), bad.cpu().numpy()
+
+    return fn
+
+
+def enhance_images(imgs, netG=None, net_vq=None, precision=None, batch=8, enhance_fn=None, names=None, device=None, report=None):
+    """uint8 HWC arrays of any sizes -> the enhanced uint8 arrays, same shapes, same order.
+
+    Images are grouped by padded shape and each group runs in batches of at most `batch`, capped by max_batch() (the DCN fast path's
+    whole-batch extents).  check_size() refuses an image outside the envelope with ValueError before anything is launched.
+    enhance_fn(batch_u8 [n,H,W,3], pads, precision) -> (uint8 [n,H,W,3], nonfinite [n]): the network call (default: the HIP path
+    over netG / net_vq).  An image whose fp16 output holds inf / NaN before the clamp is run again in bf16 and named in
+    report["bf16_rerun_images"] (as glare_amd.infer does).  report: a dict that receives that list and per-image padded sizes."""
+    names = list(names) if names is not None else ["#%d" % i for i in range(len(imgs))]
+    shapes = []
+    for nm, im in zip(names, imgs):
+        assert im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3, (nm, im.dtype, im.shape)
+        pads = harness.auto_padding(im.shape[0], im.shape[1])
+        hp, wp = im.shape[0] + pads[0] + pads[1], im.shape[1] + pads[2] + pads[3]
+        check_size(hp, wp, 1, nm)
+        shapes.append((hp, wp, pads))
+    if enhance_fn is None:
+        import torch
+
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        enhance_fn = device_enhance_fn(netG, net_vq, device)
+    groups = {}
+    for i, im in enumerate(imgs):
+        groups.setdefault((im.shape[0], im.shape[1]), []).append(i)
+    results = [None] * len(imgs)
+    reruns, per_size = [], {}
+    for (h, w), idx in groups.items():
+        t0 = time.perf_counter()
+        hp, wp, pads = shapes[idx[0]]
+        bs = max(1, min(batch, max_batch(hp, wp)))
+        for s in range(0, len(idx), bs):
+            part = idx[s:s + bs]
+            stack = _stack([imgs[i] for i in part])
+            out, bad = enhance_fn(stack, pads, precision)
+            for j, i in enumerate(part):
+                results[i] = out[j]
+                if int(bad[j]) > 0 and precision != "bf16":       # fp16 overflow: bf16 has fp32's range, same kernels
+                    results[i] = enhance_fn(_stack([imgs[i]]), pads, "bf16")[0][0]
+                    reruns.append(names[i])
+        per_size["%dx%d" % (h, w)] = round((time.perf_counter() - t0) / len(idx), 4)   # enhance_fn hands back host arrays: synchronous
+    if report is not None:
+        report["seconds_per_image_by_size"] = per_size
+        report["bf16_rerun_images"] = [n for n in names if n in reruns]
+        report["padded"] = [list(s[:2]) for s in shapes]
+    return results
+
+
+def _stack(ims):
+    """uint8 [n,H,W,3], in pinned host memory when a GPU is there (the H2D copy is then an asynchronous DMA)."""
+    a = np.stack(ims)
+    try:
+        import torch
+
+        if torch.cuda.is_available():
+            return torch.from_numpy(a).pin_memory()
+    except Exception:
+        pass
+    return a
+
+
+# ---- the driver -------------------------------------------------------------------------------------------------------------
+def load_nets(net_g=None, net_vq=None, device=None):
+    """The two networks as glare_amd.infer builds them: name-seeded, checkpoints (reference format) loaded with strict=False."""
+    from . import checkpoint
+    from . import modules as M
+    from .synthetic import seeded_init_
+
+    netG = seeded_init_(M.VQLLFLOWDeformable().eval(), 0)
+    net_vq_m = seeded_init_(M.VQModel().eval(), 1)
+    if net_g:
+        checkpoint.load_network(net_g, netG, strict=False)
+    if net_vq:
+        checkpoint.load_network(net_vq, net_vq_m, strict=False)
+    return netG.to(device), net_vq_m.to(device)
+
+
+def run(inputs, out_dir, netG=None, net_vq=None, precision=None, batch=8, enhance_fn=None, device=None):
+    """Enhance every readable image of `inputs` (files and folders) into out_dir under its basename; -> the result dict of the
+    JSON line (per-image name / size / padded size, skipped files with reasons, bf16 re-runs, seconds, images/s, MP/s)."""
+    files = list_inputs(inputs)
+    imgs, names, skipped = [], [], []
+    for f in files:
+        img, why = read_image(f)
+        if img is None:
+            skipped.append({"name": os.path.basename(f), "reason": why})
+        else:
+            imgs.append(img)
+            names.append(os.path.basename(f))
+    sync = lambda: None
+    if enhance_fn is None:
+        import torch
+
+        sync = torch.cuda.synchronize
+        if imgs:                      # warm-up at the smallest shape: weight packing, workspace growth, kernel loading
+            small = min(imgs, key=lambda a: a.shape[0] * a.shape[1])
+            enhance_images([small], netG, net_vq, precision, 1, device=device)
+        sync()
+    report = {}
+    t0 = time.perf_counter()
+    outs = enhance_images(imgs, netG, net_vq, precision, batch, enhance_fn, names, device, report)
+    sync()
+    secs = time.perf_counter() - t0          # uint8 on the host -> uint8 back on the host (excluding decode / encode of the files)
+    for nm, o in zip(names, outs):
+        write_image(os.path.join(out_dir, nm), o)
+    mp = sum(a.shape[0] * a.shape[1] for a in imgs) / 1e6
+    return {"images": [{"name": n, "size": [int(a.shape[0]), int(a.shape[1])], "padded": p} for n, a, p in
+                       zip(names, imgs, report.get("padded", []))],
+            "skipped": skipped, "bf16_rerun_images": report.get("bf16_rerun_images", []),
+            "seconds": round(secs, 4), "seconds_per_image_by_size": report.get("seconds_per_image_by_size", {}), "images_per_sec": round(len(imgs) / secs, 3) if imgs and secs > 0 else 0.0,
+            "megapixels_per_sec": round(mp / secs, 3) if imgs and secs > 0 else 0.0,
+            "timed": "uint8 in pinned host memory -> uint8 back on the host, one warm-up image first; file decode / encode excluded"}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Enhance low-light photos of any size (no ground truth needed).")
+    ap.add_argument("inputs", nargs="+", help="image files and / or folders (a folder: <dir>/*.* in natural order)")
+    ap.add_argument("--out", required=True, help="output folder; each image is written under its own basename")
+    ap.add_argument("--net-g", default=None, help="net_G checkpoint (reference format); without it the weights are name-seeded")
+    ap.add_argument("--net-vq", default=None, help="VQGAN checkpoint (reference format)")
+    ap.add_argument("--precision", choices=("fp16", "bf16"), default=None,
+                    help="16-bit format of activations and filters (default fp16; images whose fp16 output is not finite are re-run in bf16)")
+    ap.add_argument("--batch", type=int, default=8, help="images of one padded size per launch (capped by the size envelope)")
+    args = ap.parse_args(argv)
+    import torch
+
+    assert torch.cuda.is_available(), "glare_amd.enhance needs an MI355X: the HIP kernels are the only implementation"
+    device = torch.device("cuda", torch.cuda.current_device())
+    netG, net_vq = load_nets(args.net_g, args.net_vq, device)
+    res = run(args.inputs, args.out, netG, net_vq, args.precision, max(1, args.batch), device=device)
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main()

@@ -89,6 +89,75 @@ def ssim_device(restored, gts_u8):
     return torch.cat(vals).double()
 
 
+# ---- unpaired enhancement (code/infer_unpaired.py:81-136): any size, no GT, uint8 out --------------------------------
+PAD_REFLECT101, PAD_SYMMETRIC = 0, 1        # GLARE_PAD_* of include/glare_hip.h
+
+
+def auto_padding(h, w, times=16):
+    """(h1, h2, w1, w2) of auto_padding (infer_unpaired.py:81-88): up to the next multiple of `times`, split top / bottom and
+    left / right with the odd pixel at the bottom / right -- a side that is already a multiple gets times/2 + times/2."""
+    h1, w1 = (times - h % times) // 2, (times - w % times) // 2
+    return h1, (times - h % times) - h1, w1, (times - w % times) - w1
+
+
+def preprocess_unpaired_device(imgs_u8, pads=None, mode=PAD_SYMMETRIC):
+    """uint8 device tensor [B,H,W,3] -> fp32 [B,3,Hp,Wp] in the log domain, padded by `pads` = (top, bottom, left, right)
+    (default auto_padding) with cv2.BORDER_REFLECT (mode PAD_SYMMETRIC) or numpy 'reflect' (PAD_REFLECT101)."""
+    from . import _lib
+
+    _lib.require_cuda(imgs_u8)
+    assert imgs_u8.dtype == torch.uint8 and imgs_u8.dim() == 4 and imgs_u8.shape[3] == 3 and imgs_u8.is_contiguous()
+    B, H, W, _ = imgs_u8.shape
+    t, b, l, r = auto_padding(H, W) if pads is None else pads
+    out = torch.empty(B, 3, H + t + b, W + l + r, dtype=torch.float32, device=imgs_u8.device)
+    i = ctypes.c_int
+    _lib.check(_lib.main_lib().glare_harness_preprocess_pad_u8(_lib.ptr(imgs_u8), i(B), i(H), i(W), i(t), i(b), i(l), i(r), i(mode),
+                                                               _lib.ptr(out), _lib.stream_handle()), "glare_harness_preprocess_pad_u8")
+    return out
+
+
+def postprocess_unpaired_device(out_nchw, pads, h, w, want_nonfinite=False):
+    """network output [B,3,Hp,Wp] (device) -> uint8 [B,h,w,3] (device): the window at (pads[0], pads[2]), clamped and TRUNCATED to
+    uint8 as rgb() does (infer_unpaired.py:42, :129-130).  want_nonfinite: also int32 [B], the inf / NaN values of each window
+    before the clamp (the overflow flag of glare_amd.infer)."""
+    from . import _lib
+
+    _lib.require_cuda(out_nchw)
+    out_nchw = out_nchw.float().contiguous()
+    B, _, Hp, Wp = out_nchw.shape
+    lib = _lib.main_lib()
+    u8 = torch.empty(B, h, w, 3, dtype=torch.uint8, device=out_nchw.device)
+    bad = ws = None
+    nws = 0
+    if want_nonfinite:
+        lib.glare_harness_postprocess_workspace_bytes.restype = ctypes.c_size_t
+        nws = lib.glare_harness_postprocess_workspace_bytes(ctypes.c_int(B))
+        ws = torch.empty(nws, dtype=torch.uint8, device=out_nchw.device)
+        bad = torch.empty(B, dtype=torch.int32, device=out_nchw.device)
+    i = ctypes.c_int
+    _lib.check(lib.glare_harness_postprocess_u8(_lib.ptr(out_nchw), i(B), i(Hp), i(Wp), i(pads[0]), i(pads[2]), i(h), i(w), _lib.ptr(u8),
+                                                _lib.ptr(bad), _lib.ptr(ws), ctypes.c_size_t(nws), _lib.stream_handle()),
+               "glare_harness_postprocess_u8")
+    return (u8, bad) if want_nonfinite else u8
+
+
+def preprocess_unpaired(img_u8, pads=None):
+    """Host restatement: uint8 [H,W,3] -> fp32 [1,3,Hp,Wp] in the log domain, auto_padding with numpy 'symmetric' (=
+    cv2.BORDER_REFLECT), t() (:39) and log_low (:122)."""
+    t, b, l, r = auto_padding(*img_u8.shape[:2]) if pads is None else pads
+    img = np.pad(img_u8, [(t, b), (l, r), (0, 0)], "symmetric")
+    x = torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1)[None]).astype(np.float32)) / 255
+    return torch.log(torch.clamp(x + 1e-3, min=1e-3))
+
+
+def rgb_u8(x):
+    """Host restatement of rgb() (infer_unpaired.py:42): float array -> uint8 = (clip(x, 0, 1) * 255) in fp32, TRUNCATED; a NaN
+    becomes 0 (fminf / fmaxf on the device; numpy's cast of a NaN is undefined)."""
+    x = np.asarray(x, dtype=np.float32)
+    x = np.where(np.isnan(x), np.float32(0), x)
+    return (np.clip(x, np.float32(0), np.float32(1)) * np.float32(255)).astype(np.uint8)
+
+
 def preprocess(img_u8):
     """uint8 [H,W,3] -> fp32 [1,3,H+20,W+20] in the log domain."""
     img = np.pad(img_u8, [(0, PAD), (PAD, 0), (0, 0)], "reflect")

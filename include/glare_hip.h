@@ -735,6 +735,26 @@ int glare_harness_postprocess_flagged_f32(const float* out_nchw, const unsigned 
                                           int Wp, int pad, float* restored_hwc, double* psnr_or_null, int* nonfinite_or_null,
                                           void* workspace, size_t workspace_bytes, glare_stream_t stream);
 
+/* ---- the unpaired harness (code/infer_unpaired.py:81-136): photos of any size, no ground truth, uint8 out ------------------
+ * glare_harness_preprocess_pad_u8: uint8 HWC [B][H][W][3] -> fp32 NCHW [B][3][H+top+bottom][W+left+right], padded on all four
+ *   sides, then /255 (t, :39) and log(clamp(x + 1e-3, min = 1e-3)) (:122, log_low) -- the arithmetic of
+ *   glare_harness_preprocess_u8.  mode: GLARE_PAD_REFLECT101 (numpy 'reflect', what glare_harness_preprocess_u8 pads with) or
+ *   GLARE_PAD_SYMMETRIC (cv2.BORDER_REFLECT = numpy 'symmetric', the border of auto_padding, :81-88).  Pads longer than the image
+ *   fold as cv2.borderInterpolate does (period 2n - 2 / 2n; a side of one pixel repeats it).  Pads are the caller's: auto_padding
+ *   gives h1 = (16 - H % 16) // 2 on top and the rest at the bottom, 8 + 8 on a side already a multiple of 16.
+ * glare_harness_postprocess_u8: the [h][w] window at (top, left) of the network output fp32 NCHW [B][3][Hp][Wp] -> uint8 HWC
+ *   [B][h][w][3] = (uint8)(fminf(fmaxf(x, 0), 1) * 255.0f) in fp32: clamp, crop (:129-130) and rgb() (:42), which TRUNCATES
+ *   (unlike glare_harness_to_ubyte's img_as_ubyte rounding); a NaN becomes 0.  nonfinite_or_null: int32 [B], the inf / NaN values
+ *   of each window counted BEFORE the clamp (as glare_harness_postprocess_flagged_f32); it needs workspace >=
+ *   glare_harness_postprocess_workspace_bytes(B), which may be NULL without it.  B <= 65535, 3 h w < 2^31. */
+#define GLARE_PAD_REFLECT101 0
+#define GLARE_PAD_SYMMETRIC 1
+int glare_harness_preprocess_pad_u8(const unsigned char* img_hwc, int B, int H, int W, int top, int bottom, int left, int right,
+                                    int mode, float* out_nchw, glare_stream_t stream);
+int glare_harness_postprocess_u8(const float* out_nchw, int B, int Hp, int Wp, int top, int left, int h, int w,
+                                 unsigned char* out_hwc_u8, int* nonfinite_or_null, void* workspace, size_t workspace_bytes,
+                                 glare_stream_t stream);
+
 /* ---- f1: the rest of the stage-3 loss (VQLLFLOWD_model.py:209-223) -------------------------------------------------
  * glare_clamp01_f32 / _backward: sr = clamp(rec, 0, 1) with NaN -> 0 (:209-215) and torch.clamp's gradient mask.
  * MS-SSIM (modules/pytorch_msssim/__init__.py:21-98) on NHWC fp32 images: per pyramid level glare_ssim_forward_f32 writes the
