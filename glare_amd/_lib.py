@@ -4,6 +4,9 @@ The product path has no fallback: if the shared library is missing or a symbol c
 resolved, importing/using an op raises.  torch is imported first so that the HIP runtime the
 library resolves (`libamdhip64.so.7`) is the one torch already loaded -- device pointers and
 streams are then shared between torch and the kernels.
+
+Every entry point is typed once, at load, from its prototype in the header (signatures()); callers pass plain Python
+numbers, ptr() of a tensor and stream_handle(), and never set a restype or argtypes themselves.
 """
 import ctypes
 import os
@@ -43,12 +46,74 @@ class GlareError(RuntimeError):
 ERR_INVALID, ERR_LAUNCH, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3, -4     # include/glare_hip.h:37-40
 
 
+# The closed table of C types the ABI uses: any pointer (and glare_stream_t) is a void*; anything else raises.
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
+
+
+def _ctype(decl, is_return=False):
+    decl = re.sub(r"\s*\*", "*", " ".join(decl.split()))
+    if is_return and decl == "const char*":
+        return ctypes.c_char_p
+    if decl.endswith("*") or decl == "glare_stream_t":
+        return ctypes.c_void_p
+    if decl in _SCALARS:
+        return _SCALARS[decl]
+    raise GlareError("no ctypes binding for the C type %r (glare_amd/_lib.py _SCALARS)" % decl)
+
+
+def parse_prototypes(text):
+    """{name: (restype, [argtypes])} of every glare_* function prototype in C header text."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)      # `#define GLARE_PAD_SYMMETRIC 1` must not glue onto the next return type
+    text = re.sub(r"\{[^{}]*\}", " ", text.replace('extern "C" {', " "))     # struct / enum bodies
+    sigs = {}
+    for stmt in text.split(";"):
+        m = re.fullmatch(r"\s*(.*?)\b(glare_\w+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        if m is None:
+            continue
+        ret, name, params = m.groups()
+        params = [" ".join(p.split()) for p in params.split(",")]
+        argtypes = []
+        if params != ["void"]:
+            for p in params:
+                decl = re.fullmatch(r"(.+?)\s*\b\w+", p)
+                if decl is None:
+                    raise GlareError("%s: cannot parse the parameter %r" % (name, p))
+                argtypes.append(_ctype(decl.group(1)))
+        sigs[name] = (_ctype(ret, is_return=True), argtypes)
+    return sigs
+
+
+_SIGNATURES = None
+
+
+def signatures():
+    """{name: (restype, [argtypes])} of every function declared in include/glare_hip.h (parsed once)."""
+    global _SIGNATURES
+    if _SIGNATURES is None:
+        with open(HEADER_PATH) as f:
+            _SIGNATURES = parse_prototypes(f.read())
+    return _SIGNATURES
+
+
 def header_symbols():
     """Names of every function declared in include/glare_hip.h."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(glare_[a-z0-9_]+)\s*\(", text)))
+    return sorted(signatures())
+
+
+def _bind(cdll, half=False):
+    """Types every declared entry point the library exports from its header prototype, once at load: call sites pass plain Python
+    values and ctypes converts each to the declared type.  half: libglare_hip_f16.so, whose x_f16 has the signature of the declared x_bf16."""
+    for name, (restype, argtypes) in signatures().items():
+        fn = getattr(cdll, name.replace("bf16", "f16") if half else name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+
+
+def host_f32(values, n=None):
+    """A host `const float*` argument (the *_host arrays of the ABI) from a sequence of numbers: float[n], default float[len(values)]."""
+    values = [float(v) for v in values]
+    return (ctypes.c_float * (len(values) if n is None else n))(*values)
 
 
 def precision():
@@ -135,8 +200,7 @@ def lib():
             if not os.path.exists(LIB_F16_PATH):
                 raise GlareError("libglare_hip_f16.so is not built (%s): run __graft_entry__.build()" % LIB_F16_PATH)
             c = ctypes.CDLL(LIB_F16_PATH, mode=ctypes.RTLD_LOCAL)
-            c.glare_status_string.restype = ctypes.c_char_p
-            c.glare_status_string.argtypes = [ctypes.c_int]
+            _bind(c, half=True)
             _lib_f16 = _F16Lib(c)
         return _lib_f16
     return main_lib()
@@ -151,12 +215,11 @@ def main_lib():
                 "libglare_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; "
                 "g.build()'` -- there is no CPU or eager fallback." % LIB_PATH)
         try:
-            _lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
+            c = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         except OSError as e:  # pragma: no cover
             raise GlareError("cannot load %s: %s" % (LIB_PATH, e))
-        _lib.glare_status_string.restype = ctypes.c_char_p
-        _lib.glare_status_string.argtypes = [ctypes.c_int]
-        _lib.glare_version.restype = ctypes.c_int
+        _bind(c)
+        _lib = c
     return _lib
 
 
@@ -166,10 +229,8 @@ def check(status, what):
 
 
 def ptr(t):
-    """Device pointer of a tensor (or NULL for None) as a ctypes void*."""
-    if t is None:
-        return ctypes.c_void_p(0)
-    return ctypes.c_void_p(t.data_ptr())
+    """Device pointer of a tensor (None = NULL) for a pointer argument of the ABI."""
+    return None if t is None else t.data_ptr()
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -182,10 +243,10 @@ def stream_handle():
     (tools/probes/train_host_profile.py), i.e. ~12 ms of the ~1 400 launches of a training step that the HOST paces (round 6)."""
     if _raw_stream is not None:
         try:
-            return ctypes.c_void_p(_raw_stream(_cur_device()))
-        except Exception:      # no initialised HIP context (CPU-side tests of the error paths): the documented route decides what to raise
+            return _raw_stream(_cur_device())
+        except RuntimeError:   # no initialised HIP context (CPU-side tests of the error paths): the documented route decides what to raise
             pass
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def require_cuda(*tensors):

@@ -4,7 +4,6 @@ Mirrors code/infer_dataset_lol.py:113-153: reflect-pad 20 px at the bottom and t
 :71-72), HWC uint8 -> NCHW float /255 (`t`, :42), log(clamp(x + 1e-3, min=1e-3)) (:127-128,
 `log_low: true`); after the network: crop `[:, :, :h, 20:]`, clamp to [0,1], GT-mean gain with the
 cv2.COLOR_BGR2GRAY weights applied to RGB-ordered data (:142-144), PSNR (utils/utils2.py:32-36)."""
-import ctypes
 import math
 
 import numpy as np
@@ -22,8 +21,7 @@ def preprocess_device(imgs_u8):
     assert imgs_u8.dtype == torch.uint8 and imgs_u8.dim() == 4 and imgs_u8.shape[3] == 3 and imgs_u8.is_contiguous()
     B, H, W, _ = imgs_u8.shape
     out = torch.empty(B, 3, H + PAD, W + PAD, dtype=torch.float32, device=imgs_u8.device)
-    _lib.check(_lib.lib().glare_harness_preprocess_u8(_lib.ptr(imgs_u8), ctypes.c_int(B), ctypes.c_int(H), ctypes.c_int(W),
-                                                      ctypes.c_int(PAD), _lib.ptr(out), _lib.stream_handle()),
+    _lib.check(_lib.lib().glare_harness_preprocess_u8(_lib.ptr(imgs_u8), B, H, W, PAD, _lib.ptr(out), _lib.stream_handle()),
                "glare_harness_preprocess_u8")
     return out
 
@@ -38,18 +36,16 @@ def postprocess_device(out_nchw, h, w, gts_u8=None, want_nonfinite=False):
     out_nchw = out_nchw.float().contiguous()
     B, _, Hp, Wp = out_nchw.shape
     lib = _lib.lib()
-    lib.glare_harness_postprocess_workspace_bytes.restype = ctypes.c_size_t
-    nws = lib.glare_harness_postprocess_workspace_bytes(ctypes.c_int(B))
+    nws = lib.glare_harness_postprocess_workspace_bytes(B)
     ws = torch.empty(nws, dtype=torch.uint8, device=out_nchw.device)
     restored = torch.empty(B, h, w, 3, dtype=torch.float32, device=out_nchw.device)
     psnr_t = None
     if gts_u8 is not None:
         assert gts_u8.dtype == torch.uint8 and tuple(gts_u8.shape) == (B, h, w, 3) and gts_u8.is_contiguous()
         psnr_t = torch.empty(B, dtype=torch.float64, device=out_nchw.device)
-    i = ctypes.c_int
     bad = torch.empty(B, dtype=torch.int32, device=out_nchw.device) if want_nonfinite else None
-    _lib.check(lib.glare_harness_postprocess_flagged_f32(_lib.ptr(out_nchw), _lib.ptr(gts_u8), i(B), i(h), i(w), i(Hp), i(Wp), i(PAD),
-                                                         _lib.ptr(restored), _lib.ptr(psnr_t), _lib.ptr(bad), _lib.ptr(ws), ctypes.c_size_t(nws),
+    _lib.check(lib.glare_harness_postprocess_flagged_f32(_lib.ptr(out_nchw), _lib.ptr(gts_u8), B, h, w, Hp, Wp, PAD, _lib.ptr(restored),
+                                                         _lib.ptr(psnr_t), _lib.ptr(bad), _lib.ptr(ws), nws,
                                                          _lib.stream_handle()), "glare_harness_postprocess_flagged_f32")
     if want_nonfinite:
         return restored, psnr_t, bad
@@ -63,7 +59,7 @@ def to_ubyte_device(restored):
     _lib.require_cuda(restored)
     restored = restored.float().contiguous()
     out = torch.empty(restored.shape, dtype=torch.uint8, device=restored.device)
-    _lib.check(_lib.main_lib().glare_harness_to_ubyte(_lib.ptr(restored), ctypes.c_longlong(restored.numel()), _lib.ptr(out),
+    _lib.check(_lib.main_lib().glare_harness_to_ubyte(_lib.ptr(restored), restored.numel(), _lib.ptr(out),
                                                       _lib.stream_handle()), "glare_harness_to_ubyte")
     return out
 
@@ -80,8 +76,8 @@ def ssim_device(restored, gts_u8):
     restored, gts_u8 = restored.contiguous(), gts_u8.contiguous()
     B = restored.shape[0]
     x, y = torch.empty_like(restored), torch.empty_like(restored)
-    _lib.check(_lib.lib().glare_harness_ubyte_planes_f32(_lib.ptr(restored), _lib.ptr(gts_u8), ctypes.c_longlong(restored.numel()),
-                                                         _lib.ptr(x), _lib.ptr(y), _lib.stream_handle()), "glare_harness_ubyte_planes_f32")
+    _lib.check(_lib.lib().glare_harness_ubyte_planes_f32(_lib.ptr(restored), _lib.ptr(gts_u8), restored.numel(), _lib.ptr(x), _lib.ptr(y),
+                                                         _lib.stream_handle()), "glare_harness_ubyte_planes_f32")
     g = np.exp(-((np.arange(11) - 5.0) ** 2) / (2 * 1.5 ** 2))
     g = (g / g.sum()).tolist()                                   # cv2.getGaussianKernel(11, 1.5)
     C1, C2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
@@ -110,9 +106,8 @@ def preprocess_unpaired_device(imgs_u8, pads=None, mode=PAD_SYMMETRIC):
     B, H, W, _ = imgs_u8.shape
     t, b, l, r = auto_padding(H, W) if pads is None else pads
     out = torch.empty(B, 3, H + t + b, W + l + r, dtype=torch.float32, device=imgs_u8.device)
-    i = ctypes.c_int
-    _lib.check(_lib.main_lib().glare_harness_preprocess_pad_u8(_lib.ptr(imgs_u8), i(B), i(H), i(W), i(t), i(b), i(l), i(r), i(mode),
-                                                               _lib.ptr(out), _lib.stream_handle()), "glare_harness_preprocess_pad_u8")
+    _lib.check(_lib.main_lib().glare_harness_preprocess_pad_u8(_lib.ptr(imgs_u8), B, H, W, t, b, l, r, mode, _lib.ptr(out),
+                                                               _lib.stream_handle()), "glare_harness_preprocess_pad_u8")
     return out
 
 
@@ -130,13 +125,11 @@ def postprocess_unpaired_device(out_nchw, pads, h, w, want_nonfinite=False):
     bad = ws = None
     nws = 0
     if want_nonfinite:
-        lib.glare_harness_postprocess_workspace_bytes.restype = ctypes.c_size_t
-        nws = lib.glare_harness_postprocess_workspace_bytes(ctypes.c_int(B))
+        nws = lib.glare_harness_postprocess_workspace_bytes(B)
         ws = torch.empty(nws, dtype=torch.uint8, device=out_nchw.device)
         bad = torch.empty(B, dtype=torch.int32, device=out_nchw.device)
-    i = ctypes.c_int
-    _lib.check(lib.glare_harness_postprocess_u8(_lib.ptr(out_nchw), i(B), i(Hp), i(Wp), i(pads[0]), i(pads[2]), i(h), i(w), _lib.ptr(u8),
-                                                _lib.ptr(bad), _lib.ptr(ws), ctypes.c_size_t(nws), _lib.stream_handle()),
+    _lib.check(lib.glare_harness_postprocess_u8(_lib.ptr(out_nchw), B, Hp, Wp, pads[0], pads[2], h, w, _lib.ptr(u8), _lib.ptr(bad),
+                                                _lib.ptr(ws), nws, _lib.stream_handle()),
                "glare_harness_postprocess_u8")
     return (u8, bad) if want_nonfinite else u8
 

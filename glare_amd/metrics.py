@@ -10,8 +10,6 @@ default, `forward(in0, in1, normalize=False)` -> [N, 1, 1, 1], and its state-dic
 so that a checkpoint saved from the package loads with `load_state_dict`; offline the weights are whatever the caller initialises
 (glare_amd.synthetic.seeded_init_ in the tests).  Compute: csrc/metrics.hip through the C ABI (fp32 as the package; no CPU path).
 """
-import ctypes
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -19,7 +17,6 @@ import torch.nn as nn
 from . import _lib
 from .modules._base import HipModule
 
-_i, _ll, _f = ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 ALEX_CHNS = (64, 192, 384, 256, 256)                                    # lpips: self.chns for net='alex'
 # (index in torchvision's alexnet.features, cin, cout, kernel, stride, padding) of the conv that ENDS each slice (ReLU follows; slices
 # 2 and 3 start with MaxPool2d(3, 2))
@@ -39,8 +36,8 @@ def conv2d_direct(x, weight, bias=None, stride=1, padding=0, relu=False, in_shif
     b = None if bias is None else bias.detach().float().contiguous()
     sh = None if in_shift is None else in_shift.detach().float().reshape(-1).contiguous()
     sc = None if in_scale is None else in_scale.detach().float().reshape(-1).contiguous()
-    _lib.check(_lib.main_lib().glare_conv2d_direct_f32(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(b), _lib.ptr(out), _i(B), _i(Cin), _i(H), _i(W),
-                                                       _i(Cout), _i(k), _i(stride), _i(padding), _i(int(relu)), _lib.ptr(sh), _lib.ptr(sc),
+    _lib.check(_lib.main_lib().glare_conv2d_direct_f32(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(b), _lib.ptr(out), B, Cin, H, W, Cout, k,
+                                                       stride, padding, int(relu), _lib.ptr(sh), _lib.ptr(sc),
                                                        _lib.stream_handle()), "glare_conv2d_direct_f32")
     return out
 
@@ -50,7 +47,7 @@ def maxpool2d(x, kernel_size, stride):
     x = x.float().contiguous()
     B, C, H, W = x.shape
     out = torch.empty(B, C, (H - kernel_size) // stride + 1, (W - kernel_size) // stride + 1, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.main_lib().glare_maxpool2d_f32(_lib.ptr(x), _lib.ptr(out), _i(B), _i(C), _i(H), _i(W), _i(kernel_size), _i(stride),
+    _lib.check(_lib.main_lib().glare_maxpool2d_f32(_lib.ptr(x), _lib.ptr(out), B, C, H, W, kernel_size, stride,
                                                    _lib.stream_handle()), "glare_maxpool2d_f32")
     return out
 
@@ -127,19 +124,17 @@ class LPIPS(HipModule):
         f0, f1 = self.features(in0.float()), self.features(in1.float())
         B = in0.shape[0]
         lib = _lib.main_lib()
-        lib.glare_lpips_tap_workspace_bytes.restype = ctypes.c_size_t
         total = torch.empty(B, dtype=torch.float64, device=in0.device)
         per_layer = []
         for k in range(self.L):
             a, b = f0[k], f1[k]
             C, HW = a.shape[1], a.shape[2] * a.shape[3]
-            nws = lib.glare_lpips_tap_workspace_bytes(_i(B), _ll(HW))
+            nws = lib.glare_lpips_tap_workspace_bytes(B, HW)
             ws = torch.empty(nws, dtype=torch.uint8, device=a.device)
             lin = self.lins[k].model[-1].weight.detach().float().reshape(-1).contiguous()
             dst = torch.empty(B, dtype=torch.float64, device=a.device) if retPerLayer else total
-            _lib.check(lib.glare_lpips_tap_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(lin), _i(B), _i(C), _ll(HW), _f(1e-10),
-                                               _i(int(k > 0 and not retPerLayer)), _lib.ptr(dst), _lib.ptr(ws), ctypes.c_size_t(nws),
-                                               _lib.stream_handle()), "glare_lpips_tap_f32")
+            _lib.check(lib.glare_lpips_tap_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(lin), B, C, HW, 1e-10, int(k > 0 and not retPerLayer),
+                                               _lib.ptr(dst), _lib.ptr(ws), nws, _lib.stream_handle()), "glare_lpips_tap_f32")
             if retPerLayer:
                 per_layer.append(dst.float().view(B, 1, 1, 1))
         if retPerLayer:

@@ -9,7 +9,6 @@ reference's own deform_conv.py runs unmodified on top of it
 
 Like the reference (deform_conv.py:143-144) CPU tensors raise NotImplementedError: there is no CPU path.
 """
-import ctypes
 import math
 
 import torch
@@ -20,8 +19,6 @@ from torch.nn.modules.utils import _pair, _single
 
 from .... import _lib
 from ...._lib import check, ptr, stream_handle
-
-_i, _sz = ctypes.c_int, ctypes.c_size_t
 
 
 class _DeformConvExt:
@@ -44,14 +41,12 @@ class _DeformConvExt:
         if C != Ck * group:  # deform_conv_cuda.cpp:514-516
             raise RuntimeError("Input shape and kernel channels won't match: (%d vs %d)." % (C, Ck * group))
         lib = _lib.lib()
-        lib.glare_mdcn_workspace_bytes.restype = _sz
-        nws = lib.glare_mdcn_workspace_bytes(_i(B), _i(C), _i(H), _i(W), _i(Co), _i(kh), _i(kw))
+        nws = lib.glare_mdcn_workspace_bytes(B, C, H, W, Co, kh, kw)
         ws = torch.empty(int(nws), dtype=torch.uint8, device=input.device)  # replaces the callee-owned `columns`
         offset, mask = offset.contiguous(), mask.contiguous()
-        check(lib.glare_mdcn_forward_f32(ptr(input), ptr(offset), ptr(mask), ptr(weight), ptr(bias if with_bias else None),
-                                         ptr(output), _i(B), _i(C), _i(H), _i(W), _i(Co), _i(kh), _i(kw), _i(stride_h),
-                                         _i(stride_w), _i(pad_h), _i(pad_w), _i(dilation_h), _i(dilation_w), _i(group),
-                                         _i(deformable_group), ptr(ws), _sz(ws.numel()), stream_handle()),
+        check(lib.glare_mdcn_forward_f32(ptr(input), ptr(offset), ptr(mask), ptr(weight), ptr(bias if with_bias else None), ptr(output), B,
+                                         C, H, W, Co, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group,
+                                         deformable_group, ptr(ws), ws.numel(), stream_handle()),
               "glare_mdcn_forward_f32")
 
     @staticmethod
@@ -67,16 +62,13 @@ class _DeformConvExt:
         if (kh, kw) != (kernel_h, kernel_w) or C != Ck * group:
             raise RuntimeError("Input shape and kernel shape won't match")
         lib = _lib.lib()
-        lib.glare_mdcn_backward_workspace_bytes.restype = _sz
-        nws = lib.glare_mdcn_backward_workspace_bytes(_i(B), _i(C), _i(H), _i(W), _i(Co), _i(kh), _i(kw))
+        nws = lib.glare_mdcn_backward_workspace_bytes(B, C, H, W, Co, kh, kw)
         ws = torch.empty(int(nws), dtype=torch.uint8, device=input.device)
         offset, mask, grad_output = offset.contiguous(), mask.contiguous(), grad_output.contiguous()
         check(lib.glare_mdcn_backward_f32(ptr(input), ptr(offset), ptr(mask), ptr(weight), ptr(grad_output), ptr(grad_input),
-                                          ptr(grad_offset), ptr(grad_mask), ptr(grad_weight),
-                                          ptr(grad_bias if with_bias else None), _i(B), _i(C), _i(H), _i(W), _i(Co), _i(kh),
-                                          _i(kw), _i(stride_h), _i(stride_w), _i(pad_h), _i(pad_w), _i(dilation_h),
-                                          _i(dilation_w), _i(group), _i(deformable_group), ptr(ws), _sz(ws.numel()),
-                                          stream_handle()), "glare_mdcn_backward_f32")
+                                          ptr(grad_offset), ptr(grad_mask), ptr(grad_weight), ptr(grad_bias if with_bias else None), B, C, H,
+                                          W, Co, kh, kw, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, group, deformable_group,
+                                          ptr(ws), ws.numel(), stream_handle()), "glare_mdcn_backward_f32")
 
     # ---- DCN v1 (deform_conv_ext.cpp:52-104): the unmodulated operator is DCNv2 with mask == 1 and no
     # bias (same sampling rule, deform_conv_cuda_kernel.cu:190-236 vs :571-633), so the three v1 entry points run on the

@@ -7,10 +7,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import act_dtype, check, inference_precision, precision, ptr, require_cuda, stream_handle, use_precision  # noqa: F401
-
-_i = ctypes.c_int
-_ll = ctypes.c_longlong
+from ._lib import act_dtype, check, host_f32, inference_precision, precision, ptr, require_cuda, stream_handle, use_precision  # noqa: F401
 
 
 def vq_nearest(z_tokens, codebook, want_zq=True):
@@ -23,8 +20,8 @@ def vq_nearest(z_tokens, codebook, want_zq=True):
     n, dim = z_tokens.shape
     idx = torch.empty(n, dtype=torch.int64, device=z_tokens.device)
     zq = torch.empty_like(z_tokens) if want_zq else None
-    check(_lib.lib().glare_vq_nearest_f32(ptr(z_tokens), ptr(codebook), _ll(n), _i(codebook.shape[0]), _i(dim),
-                                          ptr(idx), ptr(zq), stream_handle()), "glare_vq_nearest_f32")
+    check(_lib.lib().glare_vq_nearest_f32(ptr(z_tokens), ptr(codebook), n, codebook.shape[0], dim, ptr(idx), ptr(zq),
+                                          stream_handle()), "glare_vq_nearest_f32")
     return idx, zq
 
 
@@ -37,16 +34,16 @@ class ConvDesc(ctypes.Structure):
     """Mirror of `glare_conv_desc` (include/glare_hip.h)."""
     _fields_ = [("in_", ctypes.c_void_p), ("in2", ctypes.c_void_p), ("weight_packed", ctypes.c_void_p),
                 ("bias", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("B", _i), ("H", _i), ("W", _i),
-                ("Cin", _i), ("in_pitch", _i), ("in_off", _i),
-                ("Cin2", _i), ("in2_pitch", _i), ("in2_off", _i),
-                ("Cout", _i), ("out_pitch", _i), ("out_off", _i),
-                ("res_pitch", _i), ("res_off", _i),
-                ("ksize", _i), ("stride", _i), ("upsample", _i), ("act", _i), ("out_mode", _i),
-                ("plane_pitch", _ll), ("gn_partial", ctypes.c_void_p), ("cout_tile", _i),
+                ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("Cin", ctypes.c_int), ("in_pitch", ctypes.c_int), ("in_off", ctypes.c_int),
+                ("Cin2", ctypes.c_int), ("in2_pitch", ctypes.c_int), ("in2_off", ctypes.c_int),
+                ("Cout", ctypes.c_int), ("out_pitch", ctypes.c_int), ("out_off", ctypes.c_int),
+                ("res_pitch", ctypes.c_int), ("res_off", ctypes.c_int),
+                ("ksize", ctypes.c_int), ("stride", ctypes.c_int), ("upsample", ctypes.c_int), ("act", ctypes.c_int), ("out_mode", ctypes.c_int),
+                ("plane_pitch", ctypes.c_longlong), ("gn_partial", ctypes.c_void_p), ("cout_tile", ctypes.c_int),
                 ("residual_lo", ctypes.c_void_p), ("out_lo", ctypes.c_void_p),
-                ("groups", _i), ("group_in_step", _i), ("group_out_step", _i), ("k_wrap", _i),
-                ("gn_coef", ctypes.c_void_p), ("gn_swish", _i)]
+                ("groups", ctypes.c_int), ("group_in_step", ctypes.c_int), ("group_out_step", ctypes.c_int), ("k_wrap", ctypes.c_int),
+                ("gn_coef", ctypes.c_void_p), ("gn_swish", ctypes.c_int)]
 
 
 # k_wrap = 2 (round 5): the K order of an fp32-class 3x3 conv in which every x_hi halo tile is staged ONCE for the two filter halves it
@@ -94,7 +91,7 @@ def filter_feedback_round(w):
     require_cuda(w)
     w = w.detach().float().contiguous()
     out = torch.empty_like(w)
-    check(_lib.lib().glare_filter_feedback_round_bf16(ptr(w), ptr(out), _i(w.shape[0]), _ll(w.numel() // w.shape[0]), stream_handle()),
+    check(_lib.lib().glare_filter_feedback_round_bf16(ptr(w), ptr(out), w.shape[0], w.numel() // w.shape[0], stream_handle()),
           "glare_filter_feedback_round_bf16")
     return out
 
@@ -138,8 +135,7 @@ class PackedConv:
         if self.subpixel:
             assert kh == 3 and dgrad_pad is None
             self.cout, self.cin = cout, cin
-            lib.glare_conv2d_upsample_packed_weight_elems.restype = _ll
-            n = lib.glare_conv2d_upsample_packed_weight_elems(_i(cout), _i(cin))
+            n = lib.glare_conv2d_upsample_packed_weight_elems(cout, cin)
             assert n > 0
             self.packed = torch.empty(n, dtype=act_dtype(), device=w.device)
             if feedback:
@@ -150,40 +146,39 @@ class PackedConv:
                 ph = torch.stack([torch.stack([torch.stack([w[:, :, list(rows[a][r])][:, :, :, list(rows[b][c])].sum(dim=(2, 3)) for c in (0, 1)], -1)
                                                for r in (0, 1)], -2) for a in (0, 1) for b in (0, 1)])           # [4, cout, cin, 2, 2]
                 ph = filter_feedback_round(ph.reshape(4 * cout, cin, 2, 2))
-                check(lib.glare_conv2d_pack_weight_upsample_phases(ptr(ph), _i(cout), _i(cin), ptr(self.packed), stream_handle()),
+                check(lib.glare_conv2d_pack_weight_upsample_phases(ptr(ph), cout, cin, ptr(self.packed), stream_handle()),
                       "glare_conv2d_pack_weight_upsample_phases")
             else:
-                check(lib.glare_conv2d_pack_weight_upsample(ptr(w), _i(cout), _i(cin), ptr(self.packed), stream_handle()),
+                check(lib.glare_conv2d_pack_weight_upsample(ptr(w), cout, cin, ptr(self.packed), stream_handle()),
                       "glare_conv2d_pack_weight_upsample")
             self.bias = None if bias is None else bias.detach().float().contiguous()
             return
-        lib.glare_conv2d_packed_weight_elems.restype = _ll
         self.cout, self.cin = (cout, cin) if dgrad_pad is None else (cin, dgrad_pad)
-        n = lib.glare_conv2d_packed_weight_elems(_i(self.cout), _i(self.cin), _i(kh))
+        n = lib.glare_conv2d_packed_weight_elems(self.cout, self.cin, kh)
         assert n > 0
         self.packed = torch.empty(n, dtype=act_dtype(), device=w.device)
         if dgrad_pad is None:
-            check(lib.glare_conv2d_pack_weight(ptr(w), _i(cout), _i(cin), _i(kh), ptr(self.packed), stream_handle()),
+            check(lib.glare_conv2d_pack_weight(ptr(w), cout, cin, kh, ptr(self.packed), stream_handle()),
                   "glare_conv2d_pack_weight")
         else:
-            check(lib.glare_conv2d_pack_weight_dgrad(ptr(w), _i(cout), _i(cin), _i(kh), _i(dgrad_pad), ptr(self.packed),
+            check(lib.glare_conv2d_pack_weight_dgrad(ptr(w), cout, cin, kh, dgrad_pad, ptr(self.packed),
                                                      stream_handle()), "glare_conv2d_pack_weight_dgrad")
         self.bias = None if bias is None else bias.detach().float().contiguous()
         self.w16 = None
         self.w16_lo = None
         if split:
             self.cin = cin // split          # the conv's own input channels; the packed image holds `split` K segments of them
-            if kh == 1 and split == 3 and lib.glare_conv1x1_ws_split_supported(_i(self.cin), _i(cout)):
+            if kh == 1 and split == 3 and lib.glare_conv1x1_ws_split_supported(self.cin, cout):
                 # the fp32-class form on the weight-stationary kernel: the two halves of the filter as plain [Cout][Cin] images
                 # (segment 0 of `w` is the fp32 filter -- the pack kernel rounds it to w_hi --, segment 2 is w_lo)
                 w2 = w.reshape(cout, 3, self.cin)
                 self.w16, self.w16_lo = (torch.empty(cout, self.cin, dtype=act_dtype(), device=w.device) for _ in range(2))
                 for src, dst in ((w2[:, 0].contiguous(), self.w16), (w2[:, 2].contiguous(), self.w16_lo)):
-                    check(lib.glare_conv1x1_ws_pack_weight(ptr(src), _i(cout), _i(self.cin), ptr(dst), stream_handle()), "glare_conv1x1_ws_pack_weight")
-        if kh == 1 and dgrad_pad is None and not split and lib.glare_conv1x1_ws_supported(_i(cin), _i(cout)):
+                    check(lib.glare_conv1x1_ws_pack_weight(ptr(src), cout, self.cin, ptr(dst), stream_handle()), "glare_conv1x1_ws_pack_weight")
+        if kh == 1 and dgrad_pad is None and not split and lib.glare_conv1x1_ws_supported(cin, cout):
             # the weight-stationary 1x1 kernel (csrc/conv1x1.hip) takes the filter as plain bf16 [Cout][Cin]
             self.w16 = torch.empty(cout, cin, dtype=act_dtype(), device=w.device)
-            check(lib.glare_conv1x1_ws_pack_weight(ptr(w), _i(cout), _i(cin), ptr(self.w16), stream_handle()), "glare_conv1x1_ws_pack_weight")
+            check(lib.glare_conv1x1_ws_pack_weight(ptr(w), cout, cin, ptr(self.w16), stream_handle()), "glare_conv1x1_ws_pack_weight")
 
 
 def packed_conv_batch(weights, biases=None, dgrad_pad=None, cout_tile=0, split=0):
@@ -200,13 +195,12 @@ def packed_conv_batch(weights, biases=None, dgrad_pad=None, cout_tile=0, split=0
     n, cout, cin, kh, kw = w.shape
     assert kh == kw and kh in (1, 3)
     lib = _lib.lib()
-    lib.glare_conv2d_packed_weight_elems_tile.restype = _ll
     oc, ic = (cout, cin) if dgrad_pad is None else (cin, dgrad_pad)
-    elems = lib.glare_conv2d_packed_weight_elems_tile(_i(oc), _i(ic), _i(kh), _i(cout_tile))
+    elems = lib.glare_conv2d_packed_weight_elems_tile(oc, ic, kh, cout_tile)
     assert elems > 0
     packed = torch.empty(n, elems, dtype=act_dtype(), device=w.device)
-    check(lib.glare_conv2d_pack_weight_batched(ptr(w), _i(n), _i(cout), _i(cin), _i(kh), _i(0 if dgrad_pad is None else dgrad_pad),
-                                               _i(cout_tile), ptr(packed), stream_handle()), "glare_conv2d_pack_weight_batched")
+    check(lib.glare_conv2d_pack_weight_batched(ptr(w), n, cout, cin, kh, 0 if dgrad_pad is None else dgrad_pad, cout_tile, ptr(packed),
+                                               stream_handle()), "glare_conv2d_pack_weight_batched")
     b = None if biases is None else biases.detach().float().contiguous()
     out = []
     for k in range(n):
@@ -276,8 +270,8 @@ class PackCache:
                 kinds = [(1, pc.packed)] if dgrad_pad is not None else [(0, pc.packed)] + ([(2, pc.w16)] if pc.w16 is not None else [])
                 for kind, dst in kinds:
                     j = _PackJob()
-                    check(lib.glare_conv2d_pack_job_init(ctypes.byref(j), _i(kind), ptr(pc._param), _i(cout), _i(cin), _i(kh),
-                                                         _i(dgrad_pad or 0), _i(cout_tile), ptr(dst)), "glare_conv2d_pack_job_init")
+                    check(lib.glare_conv2d_pack_job_init(ctypes.byref(j), kind, ptr(pc._param), cout, cin, kh, dgrad_pad or 0, cout_tile,
+                                                         ptr(dst)), "glare_conv2d_pack_job_init")
                     j.block_begin = begin
                     begin += (j.total + PACK_BLOCK_ELEMS - 1) // PACK_BLOCK_ELEMS
                     jobs.append(j)
@@ -286,7 +280,7 @@ class PackCache:
             dev = next(iter(self.entries.values())).packed.device
             self.table = (host.to(dev), len(jobs), begin)
         tab, n, blocks = self.table
-        check(_lib.lib().glare_conv2d_pack_multi(ptr(tab), _i(n), _ll(blocks), stream_handle()), "glare_conv2d_pack_multi")
+        check(_lib.lib().glare_conv2d_pack_multi(ptr(tab), n, blocks, stream_handle()), "glare_conv2d_pack_multi")
 
 
 PACK_CACHE = None   # the PackCache of the training step in progress (None: every packed_for() packs)
@@ -304,7 +298,7 @@ def packed_for(weight, bias=None, dgrad_pad=None, cout_tile=0):
 
 def conv_cout_tile(B, OH, OW, cout):
     """Output-channel tile (0 = the default) that gives a conv of this output size enough workgroups (glare_conv2d_cout_tile)."""
-    t = _lib.lib().glare_conv2d_cout_tile(_i(B), _i(OH), _i(OW), _i(cout))
+    t = _lib.lib().glare_conv2d_cout_tile(B, OH, OW, cout)
     return 0 if t >= (128 if cout > 64 else (64 if cout > 32 else 32)) else t
 
 
@@ -378,21 +372,20 @@ def _conv1x1_ws(x, pc, cin, in_off, act, residual, res_off, out, out_off, gn_sta
     gn_part = None
     if gn_stats:
         assert out_off == 0 and out.shape[3] == pc.cout
-        lib.glare_conv1x1_ws_gn_partial_elems.restype = _ll
-        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(_i(B), _ll(N), _i(pc.cout)), dtype=torch.float32, device=x.device)
+        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(B, N, pc.cout), dtype=torch.float32, device=x.device)
     if hilo:
         out_lo = torch.empty_like(out)
         rlo = getattr(residual, "_lo", None) if residual is not None else None
-        check(lib.glare_conv1x1_ws_hilo_bf16(ptr(x), _i(pitch), _i(in_off), ptr(pc.w16), _ll(0), ptr(pc.bias), _i(0), ptr(residual), ptr(rlo),
-                                             _i(residual.shape[3] if residual is not None else 0), _i(res_off), ptr(out), ptr(out_lo),
-                                             _i(out.shape[3]), _i(out_off), _i(B), _ll(N), _i(cin), _i(pc.cout), _i(ACT[act]), ptr(gn_part),
+        check(lib.glare_conv1x1_ws_hilo_bf16(ptr(x), pitch, in_off, ptr(pc.w16), 0, ptr(pc.bias), 0, ptr(residual), ptr(rlo),
+                                             residual.shape[3] if residual is not None else 0, res_off, ptr(out), ptr(out_lo), out.shape[3],
+                                             out_off, B, N, cin, pc.cout, ACT[act], ptr(gn_part),
                                              stream_handle()), "glare_conv1x1_ws_hilo_bf16")
         out._lo = out_lo
     else:
         _conv1x1_ws_plain(lib, x, pitch, in_off, pc, residual, res_off, out, out_off, B, N, cin, act, gn_part)
     if gn_stats:
         stats = torch.empty(B, 1, 32, 2, dtype=torch.float32, device=x.device)
-        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), _i(B), _ll(N), _i(pc.cout), stream_handle()),
+        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), B, N, pc.cout, stream_handle()),
               "glare_conv1x1_ws_gn_reduce")
         out._gn_stats = stats
     return out
@@ -410,8 +403,7 @@ def _conv1x1_ws_split(x, pc, cin, in_off, act, residual, res_off, out, out_off, 
     lib = _lib.lib()
     gn_part = None
     if gn_stats:
-        lib.glare_conv1x1_ws_gn_partial_elems.restype = _ll
-        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(_i(B), _ll(N), _i(pc.cout)), dtype=torch.float32, device=x.device)
+        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(B, N, pc.cout), dtype=torch.float32, device=x.device)
     out_lo = rlo = None
     if hilo:
         out_lo = getattr(out, "_lo", None)
@@ -420,13 +412,13 @@ def _conv1x1_ws_split(x, pc, cin, in_off, act, residual, res_off, out, out_off, 
     if residual is not None:
         assert residual.dtype == act_dtype() and residual.is_contiguous()
         rlo = getattr(residual, "_lo", None)
-    check(lib.glare_conv1x1_ws_split_bf16(ptr(x), ptr(xlo), _i(pitch), _i(in_off), ptr(pc.w16), ptr(pc.w16_lo), ptr(pc.bias), ptr(residual),
-                                          ptr(rlo), _i(residual.shape[3] if residual is not None else 0), _i(res_off), ptr(out), ptr(out_lo),
-                                          _i(out.shape[3]), _i(out_off), _i(B), _ll(N), _i(cin), _i(pc.cout), _i(ACT[act]), ptr(gn_part),
+    check(lib.glare_conv1x1_ws_split_bf16(ptr(x), ptr(xlo), pitch, in_off, ptr(pc.w16), ptr(pc.w16_lo), ptr(pc.bias), ptr(residual),
+                                          ptr(rlo), residual.shape[3] if residual is not None else 0, res_off, ptr(out), ptr(out_lo),
+                                          out.shape[3], out_off, B, N, cin, pc.cout, ACT[act], ptr(gn_part),
                                           stream_handle()), "glare_conv1x1_ws_split_bf16")
     if gn_stats:
         stats = torch.empty(B, 1, 32, 2, dtype=torch.float32, device=x.device)
-        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), _i(B), _ll(N), _i(pc.cout), stream_handle()),
+        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), B, N, pc.cout, stream_handle()),
               "glare_conv1x1_ws_gn_reduce")
         out._gn_stats = stats
     if out_lo is not None:
@@ -435,9 +427,9 @@ def _conv1x1_ws_split(x, pc, cin, in_off, act, residual, res_off, out, out_off, 
 
 
 def _conv1x1_ws_plain(lib, x, pitch, in_off, pc, residual, res_off, out, out_off, B, N, cin, act, gn_part):
-    check(lib.glare_conv1x1_ws_bf16(ptr(x), _i(pitch), _i(in_off), ptr(pc.w16), ptr(pc.bias), ptr(residual),
-                                    _i(residual.shape[3] if residual is not None else 0), _i(res_off), ptr(out), _i(out.shape[3]),
-                                    _i(out_off), _i(B), _ll(N), _i(cin), _i(pc.cout), _i(ACT[act]), ptr(gn_part), stream_handle()),
+    check(lib.glare_conv1x1_ws_bf16(ptr(x), pitch, in_off, ptr(pc.w16), ptr(pc.bias), ptr(residual),
+                                    residual.shape[3] if residual is not None else 0, res_off, ptr(out), out.shape[3], out_off, B, N, cin,
+                                    pc.cout, ACT[act], ptr(gn_part), stream_handle()),
           "glare_conv1x1_ws_bf16")
 
 
@@ -456,24 +448,23 @@ def conv1x1_per_image(x, w16, bias, residual=None, gn_stats=False, hilo=False):
     lib = _lib.lib()
     gn_part = None
     if gn_stats:
-        lib.glare_conv1x1_ws_gn_partial_elems.restype = _ll
-        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(_i(B), _ll(N), _i(cout)), dtype=torch.float32, device=x.device)
+        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(B, N, cout), dtype=torch.float32, device=x.device)
     if residual is not None:
         assert residual.dtype == act_dtype() and residual.is_contiguous() and residual.shape == out.shape
     if hilo:
         out_lo = torch.empty_like(out)
         rlo = getattr(residual, "_lo", None) if residual is not None else None
-        check(lib.glare_conv1x1_ws_hilo_bf16(ptr(x), _i(cin), _i(0), ptr(w16), _ll(cout * cin), ptr(bias), _i(cout), ptr(residual), ptr(rlo),
-                                             _i(cout if residual is not None else 0), _i(0), ptr(out), ptr(out_lo), _i(cout), _i(0), _i(B),
-                                             _ll(N), _i(cin), _i(cout), _i(0), ptr(gn_part), stream_handle()), "glare_conv1x1_ws_hilo_bf16")
+        check(lib.glare_conv1x1_ws_hilo_bf16(ptr(x), cin, 0, ptr(w16), cout * cin, ptr(bias), cout, ptr(residual), ptr(rlo),
+                                             cout if residual is not None else 0, 0, ptr(out), ptr(out_lo), cout, 0, B, N, cin, cout, 0,
+                                             ptr(gn_part), stream_handle()), "glare_conv1x1_ws_hilo_bf16")
         out._lo = out_lo
     else:
-        check(lib.glare_conv1x1_ws_image_bf16(ptr(x), _i(cin), _i(0), ptr(w16), _ll(cout * cin), ptr(bias), _i(cout), ptr(residual),
-                                              _i(cout if residual is not None else 0), _i(0), ptr(out), _i(cout), _i(0), _i(B), _ll(N),
-                                              _i(cin), _i(cout), _i(0), ptr(gn_part), stream_handle()), "glare_conv1x1_ws_image_bf16")
+        check(lib.glare_conv1x1_ws_image_bf16(ptr(x), cin, 0, ptr(w16), cout * cin, ptr(bias), cout, ptr(residual),
+                                              cout if residual is not None else 0, 0, ptr(out), cout, 0, B, N, cin, cout, 0, ptr(gn_part),
+                                              stream_handle()), "glare_conv1x1_ws_image_bf16")
     if gn_stats:
         stats = torch.empty(B, 1, 32, 2, dtype=torch.float32, device=x.device)
-        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), _i(B), _ll(N), _i(cout), stream_handle()),
+        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), B, N, cout, stream_handle()),
               "glare_conv1x1_ws_gn_reduce")
         out._gn_stats = stats
     return out
@@ -492,9 +483,9 @@ def attn_fold_groupnorm(stats, HW, gamma, beta, eps, wq, bq, wo, bo):
     wo_b = torch.empty_like(wq_b)
     bq_b = torch.empty(B, C, dtype=torch.float32, device=stats.device)
     bo_b = torch.empty_like(bq_b)
-    check(_lib.lib().glare_attn_fold_groupnorm_f32(ptr(stats), _i(splits), _i(B), _ll(HW), _i(C), ptr(gamma), ptr(beta), _f(eps), ptr(wq),
-                                                   ptr(bq), ptr(wo), ptr(bo), ptr(wq_b), ptr(bq_b), ptr(wo_b), ptr(bo_b),
-                                                   _i(int(ATTN_FOLD_FEEDBACK)), stream_handle()),
+    check(_lib.lib().glare_attn_fold_groupnorm_f32(ptr(stats), splits, B, HW, C, ptr(gamma), ptr(beta), eps, ptr(wq), ptr(bq), ptr(wo),
+                                                   ptr(bo), ptr(wq_b), ptr(bq_b), ptr(wo_b), ptr(bo_b), int(ATTN_FOLD_FEEDBACK),
+                                                   stream_handle()),
           "glare_attn_fold_groupnorm_f32")
     return wq_b, bq_b, wo_b, bo_b
 
@@ -652,12 +643,10 @@ def conv2d(x, pc, *, x2=None, cin=None, in_off=0, cin2=None, in2_off=0, stride=1
     gn_part = None
     if gn_stats:  # GroupNorm statistics of the output, gathered by the epilogue (saves the consumer's read pass)
         assert out_mode == OUT_NHWC_BF16 and pc.cout % 128 == 0 and out_off == 0 and out.shape[3] == pc.cout
-        lib.glare_conv2d_gn_partial_elems.restype = _ll
-        lib.glare_conv2d_upsample_gn_partial_elems.restype = _ll
         if subpixel:
-            n = lib.glare_conv2d_upsample_gn_partial_elems(_i(B), _i(H), _i(W), _i(pc.cout))
+            n = lib.glare_conv2d_upsample_gn_partial_elems(B, H, W, pc.cout)
         else:
-            n = lib.glare_conv2d_gn_partial_elems(_i(B), _i(OH), _i(OW), _i(pc.cout))
+            n = lib.glare_conv2d_gn_partial_elems(B, OH, OW, pc.cout)
         gn_part = torch.empty(n, dtype=torch.float32, device=x.device)
         d.gn_partial = gn_part.data_ptr()
     if LAUNCH_EVENTS is not None and pc.ksize == 3:
@@ -674,10 +663,10 @@ def conv2d(x, pc, *, x2=None, cin=None, in_off=0, cin2=None, in2_off=0, stride=1
     if gn_stats:
         stats = torch.empty(B, 1, 32, 2, dtype=torch.float32, device=x.device)
         if subpixel:
-            check(lib.glare_conv2d_upsample_gn_reduce(ptr(gn_part), ptr(stats), _i(B), _i(H), _i(W), _i(pc.cout), stream_handle()),
+            check(lib.glare_conv2d_upsample_gn_reduce(ptr(gn_part), ptr(stats), B, H, W, pc.cout, stream_handle()),
                   "glare_conv2d_upsample_gn_reduce")
         else:
-            check(lib.glare_conv2d_gn_reduce(ptr(gn_part), ptr(stats), _i(B), _i(OH), _i(OW), _i(pc.cout), stream_handle()),
+            check(lib.glare_conv2d_gn_reduce(ptr(gn_part), ptr(stats), B, OH, OW, pc.cout, stream_handle()),
                   "glare_conv2d_gn_reduce")
         out._gn_stats = stats  # consumed by groupnorm(); plain Python attribute, not a tensor property
     if out_lo is not None:
@@ -686,10 +675,6 @@ def conv2d(x, pc, *, x2=None, cin=None, in_off=0, cin2=None, in2_off=0, stride=1
 
 
 # ---- thin convs, GroupNorm, glue -------------------------------------------------------------------
-_f = ctypes.c_float
-_sz = ctypes.c_size_t
-
-
 def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
@@ -707,17 +692,15 @@ def conv2d_smallcin(x, strides, shape_bhw, weight, bias=None, act="none", out=No
         hi = torch.empty(B, H, W, cout, dtype=act_dtype(), device=x.device)
         lo = torch.empty_like(hi)
         sb, sc, sy, sx = strides
-        check(_lib.lib().glare_conv2d_smallcin_hilo_f32(ptr(x), _ll(sb), _ll(sc), _ll(sy), _ll(sx), ptr(w), ptr(b), ptr(hi), ptr(lo),
-                                                        _i(B), _i(H), _i(W), _i(cin), _i(cout), _i(k), _i(cout), _i(0), _i(ACT[act]),
-                                                        stream_handle()), "glare_conv2d_smallcin_hilo_f32")
+        check(_lib.lib().glare_conv2d_smallcin_hilo_f32(ptr(x), sb, sc, sy, sx, ptr(w), ptr(b), ptr(hi), ptr(lo), B, H, W, cin, cout, k,
+                                                        cout, 0, ACT[act], stream_handle()), "glare_conv2d_smallcin_hilo_f32")
         hi._lo = lo
         return hi
     if out is None:
         out = torch.empty(B, H, W, cout, dtype=torch.float32 if out_f32 else act_dtype(), device=x.device)
     sb, sc, sy, sx = strides
-    check(_lib.lib().glare_conv2d_smallcin_f32(ptr(x), _ll(sb), _ll(sc), _ll(sy), _ll(sx), ptr(w), ptr(b), ptr(out),
-                                               _i(B), _i(H), _i(W), _i(cin), _i(cout), _i(k), _i(out.shape[3]),
-                                               _i(out_off), _i(ACT[act]), _i(int(out.dtype == torch.float32)),
+    check(_lib.lib().glare_conv2d_smallcin_f32(ptr(x), sb, sc, sy, sx, ptr(w), ptr(b), ptr(out), B, H, W, cin, cout, k, out.shape[3],
+                                               out_off, ACT[act], int(out.dtype == torch.float32),
                                                stream_handle()), "glare_conv2d_smallcin_f32")
     return out
 
@@ -738,12 +721,11 @@ def groupnorm(x, gamma, beta, swish=True, eps=1e-6, cin=None, in_off=0, pair=Fal
         ylo = torch.empty_like(y) if pair else None      # pair: the output as a hi / lo pair too (operand of an fp32-class conv)
         ws, nws = None, 0
         if stats is None:
-            lib.glare_groupnorm_workspace_bytes.restype = _sz
-            nws = lib.glare_groupnorm_workspace_bytes(_i(B), _ll(H * W))
+            nws = lib.glare_groupnorm_workspace_bytes(B, H * W)
             ws = _workspace(nws, x.device)
-        check(lib.glare_groupnorm_hilo_pair_bf16(ptr(x), ptr(xlo), _i(pitch), _i(0), ptr(gamma), ptr(beta), ptr(y), ptr(ylo), _i(B),
-                                                 _ll(H * W), _i(C), _f(eps), _i(int(swish)), ptr(stats),
-                                                 _i(int(stats.shape[1]) if stats is not None else 0), ptr(ws), _sz(nws), stream_handle()),
+        check(lib.glare_groupnorm_hilo_pair_bf16(ptr(x), ptr(xlo), pitch, 0, ptr(gamma), ptr(beta), ptr(y), ptr(ylo), B, H * W, C, eps,
+                                                 int(swish), ptr(stats), int(stats.shape[1]) if stats is not None else 0, ptr(ws), nws,
+                                                 stream_handle()),
               "glare_groupnorm_hilo_pair_bf16")
         if pair:
             y._lo = ylo
@@ -751,16 +733,15 @@ def groupnorm(x, gamma, beta, swish=True, eps=1e-6, cin=None, in_off=0, pair=Fal
     assert not pair, "groupnorm(pair=True) normalises a hi / lo pair (x._lo)"
     if stats is not None and in_off == 0 and C == pitch:
         y = torch.empty(B, H, W, C, dtype=act_dtype(), device=x.device)
-        check(lib.glare_groupnorm_apply_bf16(ptr(x), _i(pitch), _i(0), ptr(gamma), ptr(beta), ptr(y), _i(B), _ll(H * W), _i(C),
-                                             _f(eps), _i(int(swish)), ptr(stats), _i(int(stats.shape[1])), stream_handle()),
+        check(lib.glare_groupnorm_apply_bf16(ptr(x), pitch, 0, ptr(gamma), ptr(beta), ptr(y), B, H * W, C, eps, int(swish), ptr(stats),
+                                             int(stats.shape[1]), stream_handle()),
               "glare_groupnorm_apply_bf16")
         return y
-    lib.glare_groupnorm_workspace_bytes.restype = _sz
-    nws = lib.glare_groupnorm_workspace_bytes(_i(B), _ll(H * W))
+    nws = lib.glare_groupnorm_workspace_bytes(B, H * W)
     ws = _workspace(nws, x.device)
     y = torch.empty(B, H, W, C, dtype=act_dtype(), device=x.device)
-    check(lib.glare_groupnorm_swish_bf16(ptr(x), _i(pitch), _i(in_off), ptr(gamma), ptr(beta), ptr(y), _i(B), _ll(H * W),
-                                         _i(C), _f(eps), _i(int(swish)), ptr(ws), _sz(ws.numel()), stream_handle()),
+    check(lib.glare_groupnorm_swish_bf16(ptr(x), pitch, in_off, ptr(gamma), ptr(beta), ptr(y), B, H * W, C, eps, int(swish), ptr(ws),
+                                         ws.numel(), stream_handle()),
           "glare_groupnorm_swish_bf16")
     return y
 
@@ -774,8 +755,8 @@ def groupnorm_coeffs(x, gamma, beta, eps=1e-6):
     assert stats is not None, "groupnorm_coeffs needs the producer's fused statistics on x"
     B, H, W, C = x.shape
     coef = torch.empty(B, C, 2, dtype=torch.float32, device=x.device)
-    check(_lib.lib().glare_groupnorm_coeffs_f32(ptr(stats), _i(int(stats.shape[1])), _i(B), _ll(H * W), _i(C), ptr(gamma), ptr(beta),
-                                                _f(eps), ptr(coef), stream_handle()), "glare_groupnorm_coeffs_f32")
+    check(_lib.lib().glare_groupnorm_coeffs_f32(ptr(stats), int(stats.shape[1]), B, H * W, C, ptr(gamma), ptr(beta), eps, ptr(coef),
+                                                stream_handle()), "glare_groupnorm_coeffs_f32")
     return coef
 
 
@@ -785,7 +766,7 @@ def split_hilo(x32):
     assert x32.dtype == torch.float32 and x32.is_contiguous() and x32.numel() % 8 == 0
     hi = torch.empty(x32.shape, dtype=act_dtype(), device=x32.device)
     lo = torch.empty_like(hi)
-    check(_lib.lib().glare_split_hilo_f32(ptr(x32), _ll(x32.numel()), ptr(hi), ptr(lo), stream_handle()), "glare_split_hilo_f32")
+    check(_lib.lib().glare_split_hilo_f32(ptr(x32), x32.numel(), ptr(hi), ptr(lo), stream_handle()), "glare_split_hilo_f32")
     hi._lo = lo
     return hi
 
@@ -800,12 +781,12 @@ def mix(a, b, w, out=None, out_off=0, a_off=0, b_off=0, C=None):
     if torch.is_tensor(w):   # device scalar: read by the kernel, no .item() synchronisation
         require_cuda(w)
         w32 = w.detach().float().reshape(1)
-        check(_lib.lib().glare_mix_dev_bf16(ptr(a), _i(a.shape[-1]), _i(a_off), ptr(b), _i(b.shape[-1]), _i(b_off), ptr(out),
-                                            _i(out.shape[-1]), _i(out_off), _ll(npix), _i(C), ptr(w32), stream_handle()),
+        check(_lib.lib().glare_mix_dev_bf16(ptr(a), a.shape[-1], a_off, ptr(b), b.shape[-1], b_off, ptr(out), out.shape[-1], out_off, npix,
+                                            C, ptr(w32), stream_handle()),
               "glare_mix_dev_bf16")
         return out
-    check(_lib.lib().glare_mix_bf16(ptr(a), _i(a.shape[-1]), _i(a_off), ptr(b), _i(b.shape[-1]), _i(b_off), ptr(out),
-                                    _i(out.shape[-1]), _i(out_off), _ll(npix), _i(C), _f(float(w)), stream_handle()),
+    check(_lib.lib().glare_mix_bf16(ptr(a), a.shape[-1], a_off, ptr(b), b.shape[-1], b_off, ptr(out), out.shape[-1], out_off, npix, C,
+                                    float(w), stream_handle()),
           "glare_mix_bf16")
     return out
 
@@ -817,11 +798,10 @@ def mean_rescale(h, xw, whole_batch=False):
     B = h.shape[0]
     n = h.numel() // B
     lib = _lib.lib()
-    lib.glare_mean_rescale_workspace_bytes.restype = _sz
-    ws = _workspace(lib.glare_mean_rescale_workspace_bytes(_i(B), _ll(n)), h.device)
+    ws = _workspace(lib.glare_mean_rescale_workspace_bytes(B, n), h.device)
     out = torch.empty_like(h)
-    check(lib.glare_mean_rescale_bf16(ptr(h), ptr(xw), ptr(out), _i(B), _ll(n), _i(int(whole_batch)), ptr(ws),
-                                      _sz(ws.numel()), stream_handle()), "glare_mean_rescale_bf16")
+    check(lib.glare_mean_rescale_bf16(ptr(h), ptr(xw), ptr(out), B, n, int(whole_batch), ptr(ws), ws.numel(),
+                                      stream_handle()), "glare_mean_rescale_bf16")
     return out
 
 
@@ -831,8 +811,8 @@ def nchw_to_nhwc(x, bf16=True, out=None, out_off=0):
     B, C, H, W = x.shape
     if out is None:
         out = torch.empty(B, H, W, C, dtype=act_dtype() if bf16 else torch.float32, device=x.device)
-    check(_lib.lib().glare_nchw_to_nhwc(ptr(x), ptr(out), _i(B), _i(C), _ll(H * W), _i(out.shape[3]), _i(out_off),
-                                        _i(int(out.dtype != torch.float32)), stream_handle()), "glare_nchw_to_nhwc")
+    check(_lib.lib().glare_nchw_to_nhwc(ptr(x), ptr(out), B, C, H * W, out.shape[3], out_off, int(out.dtype != torch.float32),
+                                        stream_handle()), "glare_nchw_to_nhwc")
     return out
 
 
@@ -842,8 +822,8 @@ def nhwc_to_nchw(x, C=None, off=0):
     B, H, W, pitch = x.shape
     C = pitch - off if C is None else C
     out = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
-    check(_lib.lib().glare_nhwc_to_nchw(ptr(x), ptr(out), _i(B), _i(C), _ll(H * W), _i(pitch), _i(off),
-                                        _i(int(x.dtype != torch.float32)), stream_handle()), "glare_nhwc_to_nchw")
+    check(_lib.lib().glare_nhwc_to_nchw(ptr(x), ptr(out), B, C, H * W, pitch, off, int(x.dtype != torch.float32),
+                                        stream_handle()), "glare_nhwc_to_nchw")
     return out
 
 
@@ -856,21 +836,20 @@ def flow_h1(z, ftA, ftA_off, wz, out=None):
         out = torch.empty(B, H, W, 64, dtype=act_dtype(), device=z.device)
     olo = getattr(out, "_lo", None)
     if olo is not None:        # h1 as a hi / lo pair: the operand of the fp32-class 1x1 conv that follows
-        check(_lib.lib().glare_flow_h1_pair_f32(ptr(z), ptr(ftA), _i(ftA.shape[3]), _i(ftA_off), ptr(wz), ptr(out), ptr(olo), _i(B), _i(H),
-                                                _i(W), stream_handle()), "glare_flow_h1_pair_f32")
+        check(_lib.lib().glare_flow_h1_pair_f32(ptr(z), ptr(ftA), ftA.shape[3], ftA_off, ptr(wz), ptr(out), ptr(olo), B, H, W,
+                                                stream_handle()), "glare_flow_h1_pair_f32")
         return out
-    check(_lib.lib().glare_flow_h1_f32(ptr(z), ptr(ftA), _i(ftA.shape[3]), _i(ftA_off), ptr(wz), ptr(out), _i(B), _i(H),
-                                       _i(W), stream_handle()), "glare_flow_h1_f32")
+    check(_lib.lib().glare_flow_h1_f32(ptr(z), ptr(ftA), ftA.shape[3], ftA_off, ptr(wz), ptr(out), B, H, W,
+                                       stream_handle()), "glare_flow_h1_f32")
     return out
 
 
 def flow_tail(z, h4, hF, hF_off, M, t, eps=1e-4):
     """In-place update of z fp32 [B,H,W,3]; M (9 floats) and t (3 floats) are host sequences."""
     require_cuda(z, h4, hF)
-    Ma = (ctypes.c_float * 9)(*[float(v) for v in M])
-    ta = (ctypes.c_float * 3)(*[float(v) for v in t])
-    check(_lib.lib().glare_flow_tail_f32(ptr(z), ptr(h4), ptr(hF), _i(hF.shape[3]), _i(hF_off), _ll(z.numel() // 3), Ma, ta,
-                                         _f(eps), stream_handle()), "glare_flow_tail_f32")
+    Ma, ta = host_f32(M, 9), host_f32(t, 3)
+    check(_lib.lib().glare_flow_tail_f32(ptr(z), ptr(h4), ptr(hF), hF.shape[3], hF_off, z.numel() // 3, Ma, ta, eps,
+                                         stream_handle()), "glare_flow_tail_f32")
     return z
 
 
@@ -910,7 +889,6 @@ def flow_fused_image(wz, w2, b2, w4, b4):
     parts.append(b4.detach().float().contiguous().view(torch.uint8))
     img = torch.cat(parts)
     lib = _lib.lib()
-    lib.glare_flow_step_fused_image_bytes.restype = _ll
     assert img.numel() == lib.glare_flow_step_fused_image_bytes(), img.numel()
     return img
 
@@ -920,10 +898,9 @@ def flow_step_fused(z_in, z_out, ftA, ftA_off, image, hF, hF_off, M, t, eps=1e-4
     require_cuda(z_in, z_out, ftA, image, hF)
     assert z_in.data_ptr() != z_out.data_ptr() and z_in.dtype == z_out.dtype == ftA.dtype == hF.dtype == torch.float32
     B, H, W, _ = z_in.shape
-    Ma = (ctypes.c_float * 9)(*[float(v) for v in M])
-    ta = (ctypes.c_float * 3)(*[float(v) for v in t])
-    check(_lib.lib().glare_flow_step_fused_bf16(ptr(z_in), ptr(z_out), ptr(ftA), _i(ftA.shape[3]), _i(ftA_off), ptr(image), ptr(hF),
-                                                _i(hF.shape[3]), _i(hF_off), _i(B), _i(H), _i(W), Ma, ta, _f(eps), stream_handle()),
+    Ma, ta = host_f32(M, 9), host_f32(t, 3)
+    check(_lib.lib().glare_flow_step_fused_bf16(ptr(z_in), ptr(z_out), ptr(ftA), ftA.shape[3], ftA_off, ptr(image), ptr(hF), hF.shape[3],
+                                                hF_off, B, H, W, Ma, ta, eps, stream_handle()),
           "glare_flow_step_fused_bf16")
     return z_out
 
@@ -977,24 +954,22 @@ def _attention_d512(q, k, v_t, N, ldq, ldk, out, key_splits, lse=None):
     ks = attention_key_splits(B, N) if key_splits is None else key_splits
     if lse is not None:
         lib = _lib.lib()
-        lib.glare_attention_d512_splitk_workspace_bytes.restype = _sz
-        nws = lib.glare_attention_d512_splitk_workspace_bytes(_i(B), _i(N), _i(ks))
+        nws = lib.glare_attention_d512_splitk_workspace_bytes(B, N, ks)
         ws = _workspace(nws, v_t.device) if nws else None
-        check(lib.glare_attention_d512_lse_bf16(ptr(q), _i(ldq), ptr(k), _i(ldk), ptr(v_t), _ll(v_t.shape[2]), ptr(out), _i(out.shape[-1]),
-                                                ptr(lse), _i(B), _i(N), _i(ks), ptr(ws), _sz(nws), stream_handle()),
+        check(lib.glare_attention_d512_lse_bf16(ptr(q), ldq, ptr(k), ldk, ptr(v_t), v_t.shape[2], ptr(out), out.shape[-1], ptr(lse), B, N,
+                                                ks, ptr(ws), nws, stream_handle()),
               "glare_attention_d512_lse_bf16")
         return out
     if ks > 1:
         lib = _lib.lib()
-        lib.glare_attention_d512_splitk_workspace_bytes.restype = _sz
-        nws = lib.glare_attention_d512_splitk_workspace_bytes(_i(B), _i(N), _i(ks))
+        nws = lib.glare_attention_d512_splitk_workspace_bytes(B, N, ks)
         ws = _workspace(nws, v_t.device)
-        check(lib.glare_attention_d512_splitk_bf16(ptr(q), _i(ldq), ptr(k), _i(ldk), ptr(v_t), _ll(v_t.shape[2]), ptr(out),
-                                                   _i(out.shape[-1]), _i(B), _i(N), _i(ks), ptr(ws), _sz(nws), stream_handle()),
+        check(lib.glare_attention_d512_splitk_bf16(ptr(q), ldq, ptr(k), ldk, ptr(v_t), v_t.shape[2], ptr(out), out.shape[-1], B, N, ks,
+                                                   ptr(ws), nws, stream_handle()),
               "glare_attention_d512_splitk_bf16")
         return out
-    check(_lib.lib().glare_attention_d512_bf16(ptr(q), _i(ldq), ptr(k), _i(ldk), ptr(v_t), _ll(v_t.shape[2]), ptr(out),
-                                               _i(out.shape[-1]), _i(B), _i(N), stream_handle()),
+    check(_lib.lib().glare_attention_d512_bf16(ptr(q), ldq, ptr(k), ldk, ptr(v_t), v_t.shape[2], ptr(out), out.shape[-1], B, N,
+                                               stream_handle()),
           "glare_attention_d512_bf16")
     return out
 
@@ -1016,8 +991,7 @@ def attention_kv512(q, kv, N, ldq=None, ldkv=None, out=None, key_splits=None, pa
     lib = _lib.lib()
     ws, nws = None, 0
     if ks > 1:
-        lib.glare_attention_d512_splitk_workspace_bytes.restype = _sz
-        nws = lib.glare_attention_d512_splitk_workspace_bytes(_i(B), _i(N), _i(ks))
+        nws = lib.glare_attention_d512_splitk_workspace_bytes(B, N, ks)
         ws = _workspace(nws, kv.device)
     ev = None
     if ATTENTION_LAUNCH_EVENTS is not None:
@@ -1025,12 +999,12 @@ def attention_kv512(q, kv, N, ldq=None, ldkv=None, out=None, key_splits=None, pa
         ev[0].record()
     if pair:      # the output as a hi / lo pair (`out._lo`): the operand of an fp32-class output projection
         out_lo = torch.empty_like(out)
-        check(lib.glare_attention_kv512_pair_bf16(ptr(q), _i(ldq), ptr(kv), _i(ldkv), ptr(out), ptr(out_lo), _i(out.shape[-1]), _i(B), _i(N),
-                                                  _i(ks), ptr(ws), _sz(nws), stream_handle()), "glare_attention_kv512_pair_bf16")
+        check(lib.glare_attention_kv512_pair_bf16(ptr(q), ldq, ptr(kv), ldkv, ptr(out), ptr(out_lo), out.shape[-1], B, N, ks, ptr(ws), nws,
+                                                  stream_handle()), "glare_attention_kv512_pair_bf16")
         out._lo = out_lo
     else:
-        check(lib.glare_attention_kv512_bf16(ptr(q), _i(ldq), ptr(kv), _i(ldkv), ptr(out), _i(out.shape[-1]), _i(B), _i(N), _i(ks),
-                                             ptr(ws), _sz(nws), stream_handle()), "glare_attention_kv512_bf16")
+        check(lib.glare_attention_kv512_bf16(ptr(q), ldq, ptr(kv), ldkv, ptr(out), out.shape[-1], B, N, ks, ptr(ws), nws,
+                                             stream_handle()), "glare_attention_kv512_bf16")
     if ev is not None:
         ev[1].record()
         ATTENTION_LAUNCH_EVENTS.append((ev[0], ev[1], int(B), int(N)))
@@ -1047,14 +1021,13 @@ def add_bf16(a, b, out=None, gn_stats=False):
     lib = _lib.lib()
     if gn_stats:
         B, H, W, C = a.shape
-        lib.glare_groupnorm_workspace_bytes.restype = _sz
-        nb = lib.glare_groupnorm_workspace_bytes(_i(B), _ll(H * W))
+        nb = lib.glare_groupnorm_workspace_bytes(B, H * W)
         stats = torch.empty(B, nb // (B * 256), 32, 2, dtype=torch.float32, device=a.device)
-        check(lib.glare_add_groupnorm_stats_bf16(ptr(a), ptr(b), ptr(out), _i(B), _ll(H * W), _i(C), ptr(stats), _sz(nb),
+        check(lib.glare_add_groupnorm_stats_bf16(ptr(a), ptr(b), ptr(out), B, H * W, C, ptr(stats), nb,
                                                  stream_handle()), "glare_add_groupnorm_stats_bf16")
         out._gn_stats = stats
         return out
-    check(lib.glare_add_bf16(ptr(a), ptr(b), None, ptr(out), _ll(a.numel()), stream_handle()), "glare_add_bf16")
+    check(lib.glare_add_bf16(ptr(a), ptr(b), None, ptr(out), a.numel(), stream_handle()), "glare_add_bf16")
     return out
 
 
@@ -1070,12 +1043,10 @@ def mdcn_forward(x, offset, mask, weight, bias, stride=1, padding=1, dilation=1,
     Wo = (W + 2 * padding - (dilation * (kw - 1) + 1)) // stride + 1
     out = torch.empty(B, Co, Ho, Wo, dtype=torch.float32, device=x.device)
     lib = _lib.lib()
-    lib.glare_mdcn_workspace_bytes.restype = _sz
-    ws = _workspace(lib.glare_mdcn_workspace_bytes(_i(B), _i(C), _i(H), _i(W), _i(Co), _i(kh), _i(kw)), x.device)
-    check(lib.glare_mdcn_forward_f32(ptr(x), ptr(offset), ptr(mask), ptr(weight), ptr(bias), ptr(out), _i(B), _i(C), _i(H),
-                                     _i(W), _i(Co), _i(kh), _i(kw), _i(stride), _i(stride), _i(padding), _i(padding),
-                                     _i(dilation), _i(dilation), _i(groups), _i(deformable_groups), ptr(ws),
-                                     _sz(ws.numel()), stream_handle()), "glare_mdcn_forward_f32")
+    ws = _workspace(lib.glare_mdcn_workspace_bytes(B, C, H, W, Co, kh, kw), x.device)
+    check(lib.glare_mdcn_forward_f32(ptr(x), ptr(offset), ptr(mask), ptr(weight), ptr(bias), ptr(out), B, C, H, W, Co, kh, kw, stride,
+                                     stride, padding, padding, dilation, dilation, groups, deformable_groups, ptr(ws), ws.numel(),
+                                     stream_handle()), "glare_mdcn_forward_f32")
     return out
 
 
@@ -1091,12 +1062,12 @@ class PackedDcn:
         self.single = bool(single)
         if self.single:
             self.packed = torch.empty(w.numel(), dtype=act_dtype(), device=w.device)
-            check(_lib.lib().glare_mdcn_pack_weight_single_f32(ptr(w), ptr(self.packed), _i(self.co), _i(self.c), _i(self.kh),
-                                                                _i(self.kw), _i(self.dg), stream_handle()), "glare_mdcn_pack_weight_single_f32")
+            check(_lib.lib().glare_mdcn_pack_weight_single_f32(ptr(w), ptr(self.packed), self.co, self.c, self.kh, self.kw, self.dg,
+                                                               stream_handle()), "glare_mdcn_pack_weight_single_f32")
         else:
             self.packed = torch.empty(w.numel(), dtype=torch.float32, device=w.device)
-            check(_lib.lib().glare_mdcn_pack_weight_f32(ptr(w), ptr(self.packed), _i(self.co), _i(self.c), _i(self.kh),
-                                                         _i(self.kw), _i(self.dg), stream_handle()), "glare_mdcn_pack_weight_f32")
+            check(_lib.lib().glare_mdcn_pack_weight_f32(ptr(w), ptr(self.packed), self.co, self.c, self.kh, self.kw, self.dg,
+                                                        stream_handle()), "glare_mdcn_pack_weight_f32")
         self.bias = None if bias is None else bias.detach().float().contiguous()
 
 
@@ -1125,12 +1096,10 @@ def mdcn_forward_nhwc(x, om, pd, x_off=0, C=None, mask_is_logit=True, padding=1,
 
 
 def _mdcn_forward_nhwc_launch(x, om, pd, out, mask, pitch, x_off, plane, mask_is_logit, B, C, H, W, padding, flags):
-    check(_lib.lib().glare_mdcn_forward_nhwc(ptr(x), _i(int(x.dtype != torch.float32)), _i(pitch), _i(x_off), ptr(om),
-                                             _ll(plane), _ll(om.shape[1] * plane), ctypes.c_void_p(mask.data_ptr()),
-                                             _ll(plane), _ll(om.shape[1] * plane), _i(int(mask_is_logit)),
-                                             ptr(pd.packed), ptr(pd.bias), ptr(out), _i(0), _i(pd.co), _i(0), _ll(0), _i(B),
-                                             _i(C), _i(H), _i(W), _i(pd.co), _i(pd.kh), _i(pd.kw), _i(1), _i(1), _i(padding),
-                                             _i(padding), _i(1), _i(1), _i(1), _i(pd.dg), _i(flags), stream_handle()),
+    check(_lib.lib().glare_mdcn_forward_nhwc(ptr(x), int(x.dtype != torch.float32), pitch, x_off, ptr(om), plane, om.shape[1] * plane,
+                                             ptr(mask), plane, om.shape[1] * plane, int(mask_is_logit), ptr(pd.packed), ptr(pd.bias),
+                                             ptr(out), 0, pd.co, 0, 0, B, C, H, W, pd.co, pd.kh, pd.kw, 1, 1, padding, padding, 1, 1, 1,
+                                             pd.dg, flags, stream_handle()),
           "glare_mdcn_forward_nhwc")
     return out
 
@@ -1150,17 +1119,16 @@ def mdcn_forward_nhwc_fused(x, om, pd, x_off=0, C=None, mask_is_logit=True, padd
         assert pd.packed.dtype == act_dtype()
         flags |= MDCN_SINGLE_PASS
     lib = _lib.lib()
-    tile = int(lib.glare_mdcn_tile_pixels(_i(C), _i(pd.co), _i(pd.dg), _i(flags)))
+    tile = int(lib.glare_mdcn_tile_pixels(C, pd.co, pd.dg, flags))
     out = torch.empty(B, H, W, pd.co, dtype=act_dtype() if out16 else torch.float32, device=x.device)
     sums = torch.empty(B, (H * W + tile - 1) // tile, dtype=torch.float32, device=x.device) if want_sums else None   # tiles cut per image
     mask = om[:, 2 * pd.dg * K:]
     with _timed_launch("dcn", 2.0 * B * H * W * C * pd.co * K + 8.0 * K * B * H * W * C,      # contraction + sampling; bytes: x 16-bit, offsets + mask logits fp32, output as written
                        2.0 * B * H * W * C + 4.0 * B * H * W * 3 * pd.dg * K + (2.0 if out16 else 4.0) * B * H * W * pd.co + 4.0 * pd.co * C * K):
-        check(lib.glare_mdcn_forward_nhwc_fused(ptr(x), _i(pitch), _i(x_off), ptr(om), _ll(plane), _ll(om.shape[1] * plane),
-                                                ctypes.c_void_p(mask.data_ptr()), _ll(plane), _ll(om.shape[1] * plane), _i(int(mask_is_logit)),
-                                                ptr(pd.packed), ptr(pd.bias), ptr(None if out16 else out), ptr(out if out16 else None), _i(pd.co),
-                                                _i(0), ptr(sums), _i(B), _i(C), _i(H), _i(W), _i(pd.co), _i(pd.kh), _i(pd.kw), _i(1), _i(1),
-                                                _i(padding), _i(padding), _i(1), _i(1), _i(1), _i(pd.dg), _i(flags), stream_handle()),
+        check(lib.glare_mdcn_forward_nhwc_fused(ptr(x), pitch, x_off, ptr(om), plane, om.shape[1] * plane, ptr(mask), plane,
+                                                om.shape[1] * plane, int(mask_is_logit), ptr(pd.packed), ptr(pd.bias),
+                                                ptr(None if out16 else out), ptr(out if out16 else None), pd.co, 0, ptr(sums), B, C, H, W,
+                                                pd.co, pd.kh, pd.kw, 1, 1, padding, padding, 1, 1, 1, pd.dg, flags, stream_handle()),
               "glare_mdcn_forward_nhwc_fused")
     return out, sums, tile
 
@@ -1172,11 +1140,11 @@ def mix_with_sums(a, b, w):
     B = a.shape[0]
     n = a.numel() // B
     lib = _lib.lib()
-    bps = int(lib.glare_mix_sum_blocks(_ll(n)))
+    bps = int(lib.glare_mix_sum_blocks(n))
     out = torch.empty_like(a)
     sums = torch.empty(B * bps, dtype=torch.float32, device=a.device)
     wdev = w.detach().float().reshape(1) if torch.is_tensor(w) else None
-    check(lib.glare_mix_sum_bf16(ptr(a), ptr(b), ptr(out), _i(B), _ll(n), _f(0.0 if wdev is not None else float(w)), ptr(wdev), ptr(sums),
+    check(lib.glare_mix_sum_bf16(ptr(a), ptr(b), ptr(out), B, n, 0.0 if wdev is not None else float(w), ptr(wdev), ptr(sums),
                                  stream_handle()), "glare_mix_sum_bf16")
     return out, sums
 
@@ -1191,14 +1159,14 @@ def mean_rescale_fused(h, xw, h_sums, xw_tile_sums, tile_pixels, whole_batch=Fal
     pix = n // h.shape[-1]
     out = torch.empty_like(h)
     ratio = torch.empty(B, dtype=torch.float32, device=h.device)
-    check(_lib.lib().glare_mean_rescale_fused_bf16(ptr(h), ptr(xw), _i(int(xw.dtype != torch.float32)), ptr(out), _i(B), _ll(n), _ll(pix),
-                                                   ptr(h_sums), ptr(xw_tile_sums), _i(tile_pixels), _i(int(whole_batch)), ptr(ratio),
+    check(_lib.lib().glare_mean_rescale_fused_bf16(ptr(h), ptr(xw), int(xw.dtype != torch.float32), ptr(out), B, n, pix, ptr(h_sums),
+                                                   ptr(xw_tile_sums), tile_pixels, int(whole_batch), ptr(ratio),
                                                    stream_handle()), "glare_mean_rescale_fused_bf16")
     return out
 
 
 def flow_blocks_per_sample(pixels_per_sample):
-    return int(_lib.lib().glare_flow_blocks_per_sample(_ll(pixels_per_sample)))
+    return int(_lib.lib().glare_flow_blocks_per_sample(pixels_per_sample))
 
 
 def flow_fwd_pre(z, hF, hF_off, M, t, eps, partial_row, Mt_dev=None, out=None):
@@ -1210,15 +1178,14 @@ def flow_fwd_pre(z, hF, hF_off, M, t, eps, partial_row, Mt_dev=None, out=None):
         assert Mt_dev.dtype == torch.float32 and Mt_dev.numel() == 12 and Mt_dev.is_contiguous()
         dst = z if out is None else out
         assert dst.is_contiguous() and z.is_contiguous() and dst.shape == z.shape
-        check(_lib.lib().glare_flow_fwd_pre_dev_io_f32(ptr(z), ptr(dst), ptr(hF), _i(hF.shape[3]), _i(hF_off), _i(B),
-                                                       _ll(z.numel() // 3 // B), ptr(Mt_dev), _f(eps), ptr(partial_row), stream_handle()),
+        check(_lib.lib().glare_flow_fwd_pre_dev_io_f32(ptr(z), ptr(dst), ptr(hF), hF.shape[3], hF_off, B, z.numel() // 3 // B, ptr(Mt_dev),
+                                                       eps, ptr(partial_row), stream_handle()),
               "glare_flow_fwd_pre_dev_io_f32")
         return
     assert out is None
-    Ma = (ctypes.c_float * 9)(*[float(v) for v in M])
-    ta = (ctypes.c_float * 3)(*[float(v) for v in t])
-    check(_lib.lib().glare_flow_fwd_pre_f32(ptr(z), ptr(hF), _i(hF.shape[3]), _i(hF_off), _i(B), _ll(z.numel() // 3 // B), Ma, ta,
-                                            _f(eps), ptr(partial_row), stream_handle()), "glare_flow_fwd_pre_f32")
+    Ma, ta = host_f32(M, 9), host_f32(t, 3)
+    check(_lib.lib().glare_flow_fwd_pre_f32(ptr(z), ptr(hF), hF.shape[3], hF_off, B, z.numel() // 3 // B, Ma, ta, eps, ptr(partial_row),
+                                            stream_handle()), "glare_flow_fwd_pre_f32")
 
 
 def flow_fwd_post(z, h4, eps, partial_row, out=None):
@@ -1226,7 +1193,7 @@ def flow_fwd_post(z, h4, eps, partial_row, out=None):
     B = z.shape[0]
     dst = z if out is None else out
     assert dst.is_contiguous() and z.is_contiguous() and dst.shape == z.shape
-    check(_lib.lib().glare_flow_fwd_post_io_f32(ptr(z), ptr(dst), ptr(h4), _i(B), _ll(z.numel() // 3 // B), _f(eps), ptr(partial_row),
+    check(_lib.lib().glare_flow_fwd_post_io_f32(ptr(z), ptr(dst), ptr(h4), B, z.numel() // 3 // B, eps, ptr(partial_row),
                                                 stream_handle()), "glare_flow_fwd_post_io_f32")
 
 
@@ -1235,6 +1202,6 @@ def flow_nll_reduce(z, mean, partial, n_rows):
     require_cuda(z, mean, partial)
     B = z.shape[0]
     out = torch.empty(B, 2, dtype=torch.float64, device=z.device)
-    check(_lib.lib().glare_flow_nll_reduce_f32(ptr(z), ptr(mean), ptr(partial), _i(n_rows), _i(B), _ll(z.numel() // 3 // B),
-                                               ptr(out), stream_handle()), "glare_flow_nll_reduce_f32")
+    check(_lib.lib().glare_flow_nll_reduce_f32(ptr(z), ptr(mean), ptr(partial), n_rows, B, z.numel() // 3 // B, ptr(out),
+                                               stream_handle()), "glare_flow_nll_reduce_f32")
     return out

@@ -2,18 +2,12 @@
 
 Same rules as ops.py: HIP only, no fallback, CPU tensors raise NotImplementedError.
 """
-import ctypes
-
 import torch
 
 from . import _lib
-from ._lib import act_dtype, check, ptr, require_cuda, stream_handle
+from ._lib import act_dtype, check, host_f32, ptr, require_cuda, stream_handle
 
 from .ops import count_flops as _count_flops
-
-_i = ctypes.c_int
-_ll = ctypes.c_longlong
-_f = ctypes.c_float
 
 
 def gemm_nt(a, b, out=None, alpha=1.0, out_dtype=torch.float32, accumulate=False, M=None, N=None, K=None):
@@ -37,10 +31,9 @@ def gemm_nt(a, b, out=None, alpha=1.0, out_dtype=torch.float32, accumulate=False
     o3 = out if out.dim() == 3 else out.unsqueeze(0)
     assert o3.stride(-1) == 1 and o3.dtype in (torch.float32, act_dtype())
     _count_flops("gemm_nt", 2.0 * batch * M * N * K)
-    check(_lib.lib().glare_gemm_nt_bf16(ptr(a), ptr(b), ptr(o3), _i(M), _i(N), _i(K), _ll(a.stride(1)), _ll(b.stride(1)),
-                                        _ll(o3.stride(1)), _i(batch), _ll(a.stride(0) if batch > 1 else 0),
-                                        _ll(b.stride(0) if batch > 1 else 0), _ll(o3.stride(0) if batch > 1 else 0),
-                                        _f(alpha), _i(int(o3.dtype == act_dtype())), _i(int(accumulate)), stream_handle()),
+    check(_lib.lib().glare_gemm_nt_bf16(ptr(a), ptr(b), ptr(o3), M, N, K, a.stride(1), b.stride(1), o3.stride(1), batch,
+                                        a.stride(0) if batch > 1 else 0, b.stride(0) if batch > 1 else 0, o3.stride(0) if batch > 1 else 0,
+                                        alpha, int(o3.dtype == act_dtype()), int(accumulate), stream_handle()),
           "glare_gemm_nt_bf16")
     return out[0] if squeeze and out.dim() == 3 else out
 
@@ -53,12 +46,9 @@ def reduce_parts(parts, scale=1.0, out=None, accumulate=False):
     n = parts[0].numel()
     if out is None:
         out = torch.empty(parts.shape[1:], dtype=torch.float32, device=parts.device)
-    check(_lib.lib().glare_reduce_parts_f32(ptr(parts), _i(S), _ll(n), _f(scale), ptr(out), _i(int(accumulate)), stream_handle()),
+    check(_lib.lib().glare_reduce_parts_f32(ptr(parts), S, n, scale, ptr(out), int(accumulate), stream_handle()),
           "glare_reduce_parts_f32")
     return out
-
-
-_sz = ctypes.c_size_t
 
 
 def _rup(a, b):
@@ -75,8 +65,8 @@ def transpose(x2d, ld_out=None, out=None):
     if out is None:
         out = torch.empty(batch, C, ld_out, dtype=act_dtype(), device=x2d.device)
     o3 = out if out.dim() == 3 else out.unsqueeze(0)
-    check(_lib.lib().glare_transpose_bf16(ptr(x3), _ll(x3.stride(1)), _ll(x3.stride(0) if batch > 1 else 0), ptr(o3), _ll(o3.stride(1)),
-                                          _ll(o3.stride(0) if batch > 1 else 0), _ll(R), _i(C), _i(batch), stream_handle()),
+    check(_lib.lib().glare_transpose_bf16(ptr(x3), x3.stride(1), x3.stride(0) if batch > 1 else 0, ptr(o3), o3.stride(1),
+                                          o3.stride(0) if batch > 1 else 0, R, C, batch, stream_handle()),
           "glare_transpose_bf16")
     return out if x2d.dim() == 3 else o3[0]
 
@@ -96,8 +86,8 @@ def im2col_t(x, ksize, stride=1, pad=None, upsample=False, cin=None, in_off=0, l
     if col is None:
         nrows = (cin * ksize * ksize + (1 if ones_row >= 0 else 0)) if rows is None else rows
         col = torch.empty(nrows, ldp, dtype=act_dtype(), device=x.device)
-    check(_lib.lib().glare_im2col_t_bf16(ptr(x), _i(B), _i(H), _i(W), _i(pitch), _i(in_off), _i(cin), _i(ksize), _i(stride), _i(pad),
-                                         _i(int(upsample)), ptr(col), _ll(ldp), _i(row_base), _i(ones_row), stream_handle()),
+    check(_lib.lib().glare_im2col_t_bf16(ptr(x), B, H, W, pitch, in_off, cin, ksize, stride, pad, int(upsample), ptr(col), ldp, row_base,
+                                         ones_row, stream_handle()),
           "glare_im2col_t_bf16")
     return col
 
@@ -110,8 +100,8 @@ def im2col_t_f32(x, strides, shape_bhw, cin, ksize, pad, ldp=None, ones_row=-1):
     ldp = _rup(P, 64) if ldp is None else ldp
     col = torch.empty(cin * ksize * ksize + (1 if ones_row >= 0 else 0), ldp, dtype=act_dtype(), device=x.device)
     sb, sc, sy, sx = strides
-    check(_lib.lib().glare_im2col_t_f32(ptr(x), _ll(sb), _ll(sc), _ll(sy), _ll(sx), _i(B), _i(H), _i(W), _i(cin), _i(ksize), _i(pad),
-                                        ptr(col), _ll(ldp), _i(0), _i(ones_row), stream_handle()), "glare_im2col_t_f32")
+    check(_lib.lib().glare_im2col_t_f32(ptr(x), sb, sc, sy, sx, B, H, W, cin, ksize, pad, ptr(col), ldp, 0, ones_row,
+                                        stream_handle()), "glare_im2col_t_f32")
     return col
 
 
@@ -120,7 +110,7 @@ def dilate2(g):
     assert g.dtype == act_dtype() and g.is_contiguous()
     B, OH, OW, C = g.shape
     out = torch.empty(B, 2 * OH, 2 * OW, C, dtype=act_dtype(), device=g.device)
-    check(_lib.lib().glare_dilate2_bf16(ptr(g), ptr(out), _i(B), _i(OH), _i(OW), _i(C), stream_handle()), "glare_dilate2_bf16")
+    check(_lib.lib().glare_dilate2_bf16(ptr(g), ptr(out), B, OH, OW, C, stream_handle()), "glare_dilate2_bf16")
     return out
 
 
@@ -129,7 +119,7 @@ def pool2_sum(g):
     assert g.dtype == act_dtype() and g.is_contiguous()
     B, H2, W2, C = g.shape
     out = torch.empty(B, H2 // 2, W2 // 2, C, dtype=act_dtype(), device=g.device)
-    check(_lib.lib().glare_pool2_sum_bf16(ptr(g), ptr(out), _i(B), _i(H2 // 2), _i(W2 // 2), _i(C), stream_handle()),
+    check(_lib.lib().glare_pool2_sum_bf16(ptr(g), ptr(out), B, H2 // 2, W2 // 2, C, stream_handle()),
           "glare_pool2_sum_bf16")
     return out
 
@@ -140,9 +130,8 @@ def act_backward_(g, y, act, C=None, g_off=0, y_off=0):
     from .ops import ACT
     C = g.shape[-1] - g_off if C is None else C
     pixels = g.numel() // g.shape[-1]
-    check(_lib.lib().glare_act_backward(ptr(g), _i(int(g.dtype == torch.float32)), _i(g.shape[-1]), _i(g_off), ptr(y),
-                                        _i(int(y.dtype == torch.float32)), _i(y.shape[-1]), _i(y_off), _ll(pixels), _i(C),
-                                        _i(ACT[act]), stream_handle()), "glare_act_backward")
+    check(_lib.lib().glare_act_backward(ptr(g), int(g.dtype == torch.float32), g.shape[-1], g_off, ptr(y), int(y.dtype == torch.float32),
+                                        y.shape[-1], y_off, pixels, C, ACT[act], stream_handle()), "glare_act_backward")
     return g
 
 
@@ -153,7 +142,7 @@ def cast_to_bf16(x, pitch=None):
     C = x.shape[-1]
     pitch = C if pitch is None else pitch
     out = (torch.zeros if pitch != C else torch.empty)(*x.shape[:-1], pitch, dtype=act_dtype(), device=x.device)
-    check(_lib.lib().glare_cast_f32_bf16(ptr(x), _i(C), _i(0), ptr(out), _i(pitch), _i(0), _ll(x.numel() // C), _i(C), stream_handle()),
+    check(_lib.lib().glare_cast_f32_bf16(ptr(x), C, 0, ptr(out), pitch, 0, x.numel() // C, C, stream_handle()),
           "glare_cast_f32_bf16")
     return out
 
@@ -164,7 +153,7 @@ def cast_to_f32(x, C=None):
     pitch = x.shape[-1]
     C = pitch if C is None else C
     out = torch.empty(*x.shape[:-1], C, dtype=torch.float32, device=x.device)
-    check(_lib.lib().glare_cast_bf16_f32(ptr(x), _i(pitch), _i(0), ptr(out), _i(C), _i(0), _ll(x.numel() // pitch), _i(C), stream_handle()),
+    check(_lib.lib().glare_cast_bf16_f32(ptr(x), pitch, 0, ptr(out), C, 0, x.numel() // pitch, C, stream_handle()),
           "glare_cast_bf16_f32")
     return out
 
@@ -175,12 +164,11 @@ def groupnorm_forward(x, gamma, beta, swish=True, eps=1e-6):
     assert x.dtype == act_dtype() and x.is_contiguous()
     B, H, W, C = x.shape
     lib = _lib.lib()
-    lib.glare_groupnorm_workspace_bytes.restype = _sz
-    nws = lib.glare_groupnorm_workspace_bytes(_i(B), _ll(H * W))
+    nws = lib.glare_groupnorm_workspace_bytes(B, H * W)
     stats = torch.empty(nws // 4, dtype=torch.float32, device=x.device)
     y = torch.empty_like(x)
-    check(lib.glare_groupnorm_swish_bf16(ptr(x), _i(C), _i(0), ptr(gamma), ptr(beta), ptr(y), _i(B), _ll(H * W), _i(C), _f(eps),
-                                         _i(int(swish)), ptr(stats), _sz(nws), stream_handle()), "glare_groupnorm_swish_bf16")
+    check(lib.glare_groupnorm_swish_bf16(ptr(x), C, 0, ptr(gamma), ptr(beta), ptr(y), B, H * W, C, eps, int(swish), ptr(stats), nws,
+                                         stream_handle()), "glare_groupnorm_swish_bf16")
     return y, stats.view(B, -1, 32, 2)
 
 
@@ -190,14 +178,13 @@ def groupnorm_backward(x, dy, stats, gamma, beta, swish=True, eps=1e-6):
     assert x.dtype == dy.dtype == act_dtype() and x.is_contiguous() and dy.is_contiguous()
     B, H, W, C = x.shape
     lib = _lib.lib()
-    lib.glare_groupnorm_backward_workspace_bytes.restype = _sz
-    nws = lib.glare_groupnorm_backward_workspace_bytes(_i(B), _ll(H * W), _i(C))
+    nws = lib.glare_groupnorm_backward_workspace_bytes(B, H * W, C)
     ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
     dx = torch.empty_like(x)
     per_image = torch.empty(B, 2, C, dtype=torch.float32, device=x.device)
-    check(lib.glare_groupnorm_swish_backward_bf16(ptr(x), _i(C), _i(0), ptr(dy), ptr(stats), _i(stats.shape[1]), ptr(gamma), ptr(beta),
-                                                  ptr(dx), ptr(per_image), _i(B), _ll(H * W), _i(C), _f(eps), _i(int(swish)), ptr(ws),
-                                                  _sz(nws), stream_handle()), "glare_groupnorm_swish_backward_bf16")
+    check(lib.glare_groupnorm_swish_backward_bf16(ptr(x), C, 0, ptr(dy), ptr(stats), stats.shape[1], ptr(gamma), ptr(beta), ptr(dx),
+                                                  ptr(per_image), B, H * W, C, eps, int(swish), ptr(ws), nws,
+                                                  stream_handle()), "glare_groupnorm_swish_backward_bf16")
     s = reduce_parts(per_image)
     return dx, s[1], s[0]
 
@@ -208,7 +195,7 @@ def softmax2_rows(S, n, ldp=None):
     rows = S.shape[0]
     ldp = _rup(n, 64) if ldp is None else ldp
     P = torch.empty(rows, ldp, dtype=act_dtype(), device=S.device)
-    check(_lib.lib().glare_softmax2_rows_f32(ptr(S), _ll(S.stride(0)), ptr(P), _ll(ldp), _ll(rows), _i(n), stream_handle()),
+    check(_lib.lib().glare_softmax2_rows_f32(ptr(S), S.stride(0), ptr(P), ldp, rows, n, stream_handle()),
           "glare_softmax2_rows_f32")
     return P
 
@@ -217,9 +204,8 @@ def attention_ds(P, dP, dO, O, n, scale):
     require_cuda(P, dP, dO, O)
     rows, d = dO.shape
     dS = torch.empty(rows, P.shape[1], dtype=act_dtype(), device=P.device)
-    check(_lib.lib().glare_attention_ds_bf16(ptr(P), _ll(P.stride(0)), ptr(dP), _ll(dP.stride(0)), ptr(dO), _i(dO.stride(0)), ptr(O),
-                                             _i(O.stride(0)), _i(d), ptr(dS), _ll(dS.stride(0)), _ll(rows), _i(n), _f(scale),
-                                             stream_handle()), "glare_attention_ds_bf16")
+    check(_lib.lib().glare_attention_ds_bf16(ptr(P), P.stride(0), ptr(dP), dP.stride(0), ptr(dO), dO.stride(0), ptr(O), O.stride(0), d,
+                                             ptr(dS), dS.stride(0), rows, n, scale, stream_handle()), "glare_attention_ds_bf16")
     return dS
 
 
@@ -227,8 +213,8 @@ def adam_step_(w, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1
     require_cuda(w, grad, exp_avg, exp_avg_sq)
     for t in (w, grad, exp_avg, exp_avg_sq):
         assert t.dtype == torch.float32 and t.is_contiguous()
-    check(_lib.lib().glare_adam_step_f32(ptr(w), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), _ll(w.numel()), _f(lr), _f(betas[0]),
-                                         _f(betas[1]), _f(eps), _f(weight_decay), _i(step), _f(grad_scale), stream_handle()),
+    check(_lib.lib().glare_adam_step_f32(ptr(w), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), w.numel(), lr, betas[0], betas[1], eps,
+                                         weight_decay, step, grad_scale, stream_handle()),
           "glare_adam_step_f32")
     return w
 
@@ -273,11 +259,10 @@ def attention_backward_fused(q, k, v, o, do, lse, ln2_scale=0.6931471805599453):
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     _count_flops("attn bwd", 10.0 * B * N * N * d)     # the five products of the backward (the kernel recomputes two more)
     lib = _lib.lib()
-    lib.glare_attention_d512_backward_workspace_bytes.restype = ctypes.c_size_t
-    nws = lib.glare_attention_d512_backward_workspace_bytes(_i(B), _i(N))
+    nws = lib.glare_attention_d512_backward_workspace_bytes(B, N)
     ws = torch.empty(nws, dtype=torch.uint8, device=q.device)
-    check(lib.glare_attention_d512_backward_bf16(ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), ptr(dq), ptr(dk), ptr(dv), _i(B), _i(N),
-                                                 _f(ln2_scale), ptr(ws), _sz(nws), stream_handle()), "glare_attention_d512_backward_bf16")
+    check(lib.glare_attention_d512_backward_bf16(ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), ptr(dq), ptr(dk), ptr(dv), B, N,
+                                                 ln2_scale, ptr(ws), nws, stream_handle()), "glare_attention_d512_backward_bf16")
     return dq, dk, dv
 
 
@@ -301,15 +286,11 @@ def attention_backward(q, k, v, o, do, ln2_scale=0.6931471805599453):
 
 
 # ---- flow (normal direction) backward -------------------------------------------------------------------
-def _host3(M, t):
-    return (ctypes.c_float * 9)(*[float(v) for v in M]), (ctypes.c_float * 3)(*[float(v) for v in t])
-
-
 def flow_nll_backward(z, mean, g_logp):
     require_cuda(z, mean, g_logp)
     B = z.shape[0]
     gz, gmean = torch.empty_like(z), torch.empty_like(z)
-    check(_lib.lib().glare_flow_nll_backward_f32(ptr(z), ptr(mean), ptr(g_logp), _i(B), _ll(z.numel() // 3 // B), ptr(gz), ptr(gmean),
+    check(_lib.lib().glare_flow_nll_backward_f32(ptr(z), ptr(mean), ptr(g_logp), B, z.numel() // 3 // B, ptr(gz), ptr(gmean),
                                                  stream_handle()), "glare_flow_nll_backward_f32")
     return gz, gmean
 
@@ -319,8 +300,8 @@ def flow_post_backward_(gz, z_pre, h4, g_logdet, eps, out=None):
     require_cuda(gz, z_pre, h4, g_logdet, out)
     B = gz.shape[0]
     gh4 = torch.empty(*gz.shape[:-1], 8, dtype=act_dtype(), device=gz.device) if out is None else out
-    check(_lib.lib().glare_flow_fwd_post_backward_f32(ptr(gz), ptr(z_pre), ptr(h4), ptr(g_logdet), _i(B), _ll(gz.numel() // 3 // B),
-                                                      _f(eps), ptr(gh4), stream_handle()), "glare_flow_fwd_post_backward_f32")
+    check(_lib.lib().glare_flow_fwd_post_backward_f32(ptr(gz), ptr(z_pre), ptr(h4), ptr(g_logdet), B, gz.numel() // 3 // B, eps, ptr(gh4),
+                                                      stream_handle()), "glare_flow_fwd_post_backward_f32")
     return gh4
 
 
@@ -329,9 +310,9 @@ def flow_h1_backward_(gz, g, g_off, z_pre, wz, out=None):
     require_cuda(gz, g, z_pre, wz)
     B, H, W, _ = gz.shape
     lib = _lib.lib()
-    nb = int(lib.glare_flow_bwd_blocks(_ll(B * H * W)))
+    nb = int(lib.glare_flow_bwd_blocks(B * H * W))
     part = torch.empty(nb, 576, dtype=torch.float32, device=gz.device)
-    check(lib.glare_flow_h1_backward_f32(ptr(gz), ptr(g), _i(g.shape[-1]), _i(g_off), ptr(z_pre), ptr(wz), _i(B), _i(H), _i(W), ptr(part),
+    check(lib.glare_flow_h1_backward_f32(ptr(gz), ptr(g), g.shape[-1], g_off, ptr(z_pre), ptr(wz), B, H, W, ptr(part),
                                          stream_handle()), "glare_flow_h1_backward_f32")
     return reduce_parts(part, out=None if out is None else out.view(576)).view(64, 9)
 
@@ -342,17 +323,17 @@ def flow_pre_backward_(gz, z_in, hF, hF_off, g_logdet, M, t, eps, ghF, ghF_off, 
     B = gz.shape[0]
     lib = _lib.lib()
     npix = gz.numel() // 3
-    nb = int(lib.glare_flow_bwd_blocks(_ll(npix)))
+    nb = int(lib.glare_flow_bwd_blocks(npix))
     part = torch.empty(nb, 12, dtype=torch.float32, device=gz.device)
     if Mt_dev is not None:
-        check(lib.glare_flow_fwd_pre_backward_dev_f32(ptr(gz), ptr(z_in), ptr(hF), _i(hF.shape[-1]), _i(hF_off), ptr(g_logdet), _i(B),
-                                                      _ll(npix // B), ptr(Mt_dev), _f(eps), ptr(ghF), _i(ghF.shape[-1]), _i(ghF_off),
-                                                      ptr(part), stream_handle()), "glare_flow_fwd_pre_backward_dev_f32")
+        check(lib.glare_flow_fwd_pre_backward_dev_f32(ptr(gz), ptr(z_in), ptr(hF), hF.shape[-1], hF_off, ptr(g_logdet), B, npix // B,
+                                                      ptr(Mt_dev), eps, ptr(ghF), ghF.shape[-1], ghF_off, ptr(part),
+                                                      stream_handle()), "glare_flow_fwd_pre_backward_dev_f32")
         r = reduce_parts(part, out=out)
         return r[:9].view(3, 3), r[9:]
-    Ma, ta = _host3(M, t)
-    check(lib.glare_flow_fwd_pre_backward_f32(ptr(gz), ptr(z_in), ptr(hF), _i(hF.shape[-1]), _i(hF_off), ptr(g_logdet), _i(B),
-                                              _ll(npix // B), Ma, ta, _f(eps), ptr(ghF), _i(ghF.shape[-1]), _i(ghF_off), ptr(part),
+    Ma, ta = host_f32(M, 9), host_f32(t, 3)
+    check(lib.glare_flow_fwd_pre_backward_f32(ptr(gz), ptr(z_in), ptr(hF), hF.shape[-1], hF_off, ptr(g_logdet), B, npix // B, Ma, ta, eps,
+                                              ptr(ghF), ghF.shape[-1], ghF_off, ptr(part),
                                               stream_handle()), "glare_flow_fwd_pre_backward_f32")
     r = reduce_parts(part, out=out)
     return r[:9].view(3, 3), r[9:]
@@ -369,11 +350,11 @@ def mix_backward(g, a, b, w, want_ga=False):
     ws = torch.empty(512, dtype=torch.float32, device=g.device)
     if torch.is_tensor(w):
         w32 = w.detach().float().reshape(1)
-        check(_lib.lib().glare_mix_backward_dev_bf16(ptr(g), ptr(a), ptr(b), ptr(ga), ptr(gb), _ll(g.numel()), ptr(w32), ptr(dw), ptr(ws),
-                                                     _sz(2048), stream_handle()), "glare_mix_backward_dev_bf16")
+        check(_lib.lib().glare_mix_backward_dev_bf16(ptr(g), ptr(a), ptr(b), ptr(ga), ptr(gb), g.numel(), ptr(w32), ptr(dw), ptr(ws), 2048,
+                                                     stream_handle()), "glare_mix_backward_dev_bf16")
         return ga, gb, dw
-    check(_lib.lib().glare_mix_backward_bf16(ptr(g), ptr(a), ptr(b), ptr(ga), ptr(gb), _ll(g.numel()), _f(float(w)), ptr(dw), ptr(ws),
-                                             _sz(2048), stream_handle()), "glare_mix_backward_bf16")
+    check(_lib.lib().glare_mix_backward_bf16(ptr(g), ptr(a), ptr(b), ptr(ga), ptr(gb), g.numel(), float(w), ptr(dw), ptr(ws), 2048,
+                                             stream_handle()), "glare_mix_backward_bf16")
     return ga, gb, dw
 
 
@@ -384,12 +365,11 @@ def mean_rescale_backward(g, h, xw, whole_batch):
     B = h.shape[0]
     n = h.numel() // B
     lib = _lib.lib()
-    lib.glare_mean_rescale_backward_workspace_bytes.restype = _sz
-    nws = lib.glare_mean_rescale_backward_workspace_bytes(_i(B), _ll(n))
+    nws = lib.glare_mean_rescale_backward_workspace_bytes(B, n)
     ws = torch.empty(nws, dtype=torch.uint8, device=h.device)
     gh, gxw = torch.empty_like(h), torch.empty_like(xw)
-    check(lib.glare_mean_rescale_backward_bf16(ptr(g), ptr(h), ptr(xw), ptr(gh), ptr(gxw), _i(B), _ll(n), _i(int(whole_batch)), ptr(ws),
-                                               _sz(nws), stream_handle()), "glare_mean_rescale_backward_bf16")
+    check(lib.glare_mean_rescale_backward_bf16(ptr(g), ptr(h), ptr(xw), ptr(gh), ptr(gxw), B, n, int(whole_batch), ptr(ws), nws,
+                                               stream_handle()), "glare_mean_rescale_backward_bf16")
     return gh, gxw
 
 
@@ -397,7 +377,7 @@ def sigmoid(x):
     require_cuda(x)
     assert x.dtype == torch.float32 and x.is_contiguous()
     y = torch.empty_like(x)
-    check(_lib.lib().glare_sigmoid_f32(ptr(x), ptr(y), _ll(x.numel()), stream_handle()), "glare_sigmoid_f32")
+    check(_lib.lib().glare_sigmoid_f32(ptr(x), ptr(y), x.numel(), stream_handle()), "glare_sigmoid_f32")
     return y
 
 
@@ -410,8 +390,8 @@ def l1_clamp_loss(rec_nhwc, gt_nchw):
     loss = torch.empty(1, dtype=torch.float32, device=rec_nhwc.device)
     grad = torch.empty_like(rec_nhwc)
     ws = torch.empty(512, dtype=torch.float32, device=rec_nhwc.device)
-    check(_lib.lib().glare_l1_clamp_loss_f32(ptr(rec_nhwc), ptr(gt_nchw), _i(B), _ll(H * W), _i(C), ptr(loss), ptr(grad), ptr(ws),
-                                             _sz(2048), stream_handle()), "glare_l1_clamp_loss_f32")
+    check(_lib.lib().glare_l1_clamp_loss_f32(ptr(rec_nhwc), ptr(gt_nchw), B, H * W, C, ptr(loss), ptr(grad), ptr(ws), 2048,
+                                             stream_handle()), "glare_l1_clamp_loss_f32")
     return loss, grad
 
 
@@ -420,7 +400,7 @@ def clamp01(x):
     require_cuda(x)
     assert x.dtype == torch.float32 and x.is_contiguous()
     y = torch.empty_like(x)
-    check(_lib.lib().glare_clamp01_f32(ptr(x), ptr(y), _ll(x.numel()), stream_handle()), "glare_clamp01_f32")
+    check(_lib.lib().glare_clamp01_f32(ptr(x), ptr(y), x.numel(), stream_handle()), "glare_clamp01_f32")
     return y
 
 
@@ -428,7 +408,7 @@ def clamp01_backward(x, g):
     require_cuda(x, g)
     g = g.contiguous()
     gx = torch.empty_like(x)
-    check(_lib.lib().glare_clamp01_backward_f32(ptr(x), ptr(g), ptr(gx), _ll(x.numel()), stream_handle()), "glare_clamp01_backward_f32")
+    check(_lib.lib().glare_clamp01_backward_f32(ptr(x), ptr(g), ptr(gx), x.numel(), stream_handle()), "glare_clamp01_backward_f32")
     return gx
 
 
@@ -437,12 +417,8 @@ def avgpool2(x):
     assert x.dtype == torch.float32 and x.is_contiguous()
     B, H, W, C = x.shape
     y = torch.empty(B, H // 2, W // 2, C, dtype=torch.float32, device=x.device)
-    check(_lib.lib().glare_avgpool2_f32(ptr(x), ptr(y), _i(B), _i(H), _i(W), _i(C), stream_handle()), "glare_avgpool2_f32")
+    check(_lib.lib().glare_avgpool2_f32(ptr(x), ptr(y), B, H, W, C, stream_handle()), "glare_avgpool2_f32")
     return y
-
-
-def _win(window):
-    return (ctypes.c_float * len(window))(*[float(v) for v in window])
 
 
 def ssim_forward(x, y, window, C1, C2):
@@ -451,13 +427,12 @@ def ssim_forward(x, y, window, C1, C2):
     B, H, W, C = x.shape
     ws = len(window)
     lib = _lib.lib()
-    lib.glare_ssim_workspace_bytes.restype = _sz
     nws = lib.glare_ssim_workspace_bytes()
     wsb = torch.empty(nws, dtype=torch.uint8, device=x.device)
     mom = torch.empty(B, H - ws + 1, W - ws + 1, C, 5, dtype=torch.float32, device=x.device)
     out = torch.empty(2, dtype=torch.float32, device=x.device)
-    check(lib.glare_ssim_forward_f32(ptr(x), ptr(y), _i(B), _i(H), _i(W), _i(C), _win(window), _i(ws), _f(C1), _f(C2), ptr(mom), ptr(out),
-                                     ptr(wsb), _sz(nws), stream_handle()), "glare_ssim_forward_f32")
+    check(lib.glare_ssim_forward_f32(ptr(x), ptr(y), B, H, W, C, host_f32(window), ws, C1, C2, ptr(mom), ptr(out), ptr(wsb), nws,
+                                     stream_handle()), "glare_ssim_forward_f32")
     return mom, out
 
 
@@ -466,8 +441,8 @@ def ssim_backward(x, y, mom, window, C1, C2, g10, level, g_next):
     B, H, W, C = x.shape
     scratch = torch.empty(mom.shape[:-1] + (3,), dtype=torch.float32, device=x.device)
     gx = torch.empty_like(x)
-    check(_lib.lib().glare_ssim_backward_f32(ptr(x), ptr(y), ptr(mom), _i(B), _i(H), _i(W), _i(C), _win(window), _i(len(window)), _f(C1),
-                                             _f(C2), ptr(g10), _i(level), ptr(g_next), ptr(scratch), ptr(gx), stream_handle()),
+    check(_lib.lib().glare_ssim_backward_f32(ptr(x), ptr(y), ptr(mom), B, H, W, C, host_f32(window), len(window), C1, C2, ptr(g10), level,
+                                             ptr(g_next), ptr(scratch), ptr(gx), stream_handle()),
           "glare_ssim_backward_f32")
     return gx
 
@@ -477,7 +452,7 @@ def maxpool2(x):
     assert x.dtype == act_dtype() and x.is_contiguous()
     B, H, W, C = x.shape
     y = torch.empty(B, H // 2, W // 2, C, dtype=act_dtype(), device=x.device)
-    check(_lib.lib().glare_maxpool2_bf16(ptr(x), ptr(y), _i(B), _i(H), _i(W), _i(C), stream_handle()), "glare_maxpool2_bf16")
+    check(_lib.lib().glare_maxpool2_bf16(ptr(x), ptr(y), B, H, W, C, stream_handle()), "glare_maxpool2_bf16")
     return y
 
 
@@ -486,7 +461,7 @@ def maxpool2_backward(x, g):
     B, H, W, C = x.shape
     g = g.contiguous()
     gx = torch.empty_like(x)
-    check(_lib.lib().glare_maxpool2_backward_bf16(ptr(x), ptr(g), ptr(gx), _i(B), _i(H), _i(W), _i(C), stream_handle()),
+    check(_lib.lib().glare_maxpool2_backward_bf16(ptr(x), ptr(g), ptr(gx), B, H, W, C, stream_handle()),
           "glare_maxpool2_backward_bf16")
     return gx
 
@@ -498,7 +473,7 @@ def mse_loss(a, b, want_grad=True):
     loss = torch.empty(1, dtype=torch.float32, device=a.device)
     ga = torch.empty_like(a) if want_grad else None
     ws = torch.empty(256, dtype=torch.float64, device=a.device)
-    check(_lib.lib().glare_mse_loss_bf16(ptr(a), ptr(b), _ll(a.numel()), ptr(loss), ptr(ga), ptr(ws), _sz(2048), stream_handle()),
+    check(_lib.lib().glare_mse_loss_bf16(ptr(a), ptr(b), a.numel(), ptr(loss), ptr(ga), ptr(ws), 2048, stream_handle()),
           "glare_mse_loss_bf16")
     return loss, ga
 
@@ -509,20 +484,20 @@ def mse_backward(a, b, g):
     assert a.dtype == b.dtype == act_dtype() and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
     assert g.dtype == torch.float32 and g.numel() == 1
     ga = torch.empty_like(a)
-    check(_lib.lib().glare_mse_backward_bf16(ptr(a), ptr(b), _ll(a.numel()), ptr(g), ptr(ga), stream_handle()), "glare_mse_backward_bf16")
+    check(_lib.lib().glare_mse_backward_bf16(ptr(a), ptr(b), a.numel(), ptr(g), ptr(ga), stream_handle()), "glare_mse_backward_bf16")
     return ga
 
 
 def adam_prepare_(step_dev, state3, betas):
     require_cuda(step_dev, state3)
     assert step_dev.dtype == torch.int32 and state3.dtype == torch.float32 and state3.numel() == 3
-    check(_lib.lib().glare_adam_prepare(ptr(step_dev), ptr(state3), _f(betas[0]), _f(betas[1]), stream_handle()), "glare_adam_prepare")
+    check(_lib.lib().glare_adam_prepare(ptr(step_dev), ptr(state3), betas[0], betas[1], stream_handle()), "glare_adam_prepare")
 
 
 def adam_step_dev_(w, grad, exp_avg, exp_avg_sq, state3, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     require_cuda(w, grad, exp_avg, exp_avg_sq, state3)
-    check(_lib.lib().glare_adam_step_dev_f32(ptr(w), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), _ll(w.numel()), _f(lr), _f(betas[0]),
-                                             _f(betas[1]), _f(eps), _f(weight_decay), ptr(state3), _f(grad_scale), stream_handle()),
+    check(_lib.lib().glare_adam_step_dev_f32(ptr(w), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), w.numel(), lr, betas[0], betas[1], eps,
+                                             weight_decay, ptr(state3), grad_scale, stream_handle()),
           "glare_adam_step_dev_f32")
     return w
 
@@ -531,12 +506,12 @@ def grad_nonfinite_(grad, found):
     """found (int32 [1], device) |= any(grad is inf / NaN): GradScaler's found_inf without a host read."""
     require_cuda(grad, found)
     assert grad.dtype == torch.float32 and grad.is_contiguous() and found.dtype == torch.int32
-    check(_lib.lib().glare_grad_nonfinite_f32(ptr(grad), _ll(grad.numel()), ptr(found), stream_handle()), "glare_grad_nonfinite_f32")
+    check(_lib.lib().glare_grad_nonfinite_f32(ptr(grad), grad.numel(), ptr(found), stream_handle()), "glare_grad_nonfinite_f32")
 
 
 def adam_prepare_guarded_(step_dev, state3, betas, skip):
     require_cuda(step_dev, state3, skip)
-    check(_lib.lib().glare_adam_prepare_guarded(ptr(step_dev), ptr(state3), _f(betas[0]), _f(betas[1]), ptr(skip), stream_handle()),
+    check(_lib.lib().glare_adam_prepare_guarded(ptr(step_dev), ptr(state3), betas[0], betas[1], ptr(skip), stream_handle()),
           "glare_adam_prepare_guarded")
 
 
@@ -544,21 +519,21 @@ def adam_step_dev_guarded_(w, grad, exp_avg, exp_avg_sq, state3, lr, betas, eps,
     """loss_scale: fp32 device tensor [1] the loss was multiplied by (fp16 training: GradScaler's scale), divided out here."""
     require_cuda(w, grad, exp_avg, exp_avg_sq, state3, skip, loss_scale)
     if loss_scale is not None:
-        check(_lib.lib().glare_adam_step_dev_scaled_f32(ptr(w), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), _ll(w.numel()), _f(lr),
-                                                        _f(betas[0]), _f(betas[1]), _f(eps), _f(weight_decay), ptr(state3), _f(grad_scale),
-                                                        ptr(loss_scale), ptr(skip), stream_handle()), "glare_adam_step_dev_scaled_f32")
+        check(_lib.lib().glare_adam_step_dev_scaled_f32(ptr(w), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), w.numel(), lr, betas[0], betas[1],
+                                                        eps, weight_decay, ptr(state3), grad_scale, ptr(loss_scale), ptr(skip),
+                                                        stream_handle()), "glare_adam_step_dev_scaled_f32")
         return w
-    check(_lib.lib().glare_adam_step_dev_guarded_f32(ptr(w), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), _ll(w.numel()), _f(lr),
-                                                     _f(betas[0]), _f(betas[1]), _f(eps), _f(weight_decay), ptr(state3), _f(grad_scale),
-                                                     ptr(skip), stream_handle()), "glare_adam_step_dev_guarded_f32")
+    check(_lib.lib().glare_adam_step_dev_guarded_f32(ptr(w), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), w.numel(), lr, betas[0], betas[1],
+                                                     eps, weight_decay, ptr(state3), grad_scale, ptr(skip),
+                                                     stream_handle()), "glare_adam_step_dev_guarded_f32")
     return w
 
 
 def gradscaler_update_(scale, tracker, found, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
     require_cuda(scale, tracker, found)
     assert scale.dtype == torch.float32 and tracker.dtype == torch.int32 and found.dtype == torch.int32
-    check(_lib.lib().glare_gradscaler_update(ptr(scale), ptr(tracker), ptr(found), _f(growth_factor), _f(backoff_factor),
-                                             _i(growth_interval), stream_handle()), "glare_gradscaler_update")
+    check(_lib.lib().glare_gradscaler_update(ptr(scale), ptr(tracker), ptr(found), growth_factor, backoff_factor, growth_interval,
+                                             stream_handle()), "glare_gradscaler_update")
 
 
 def actnorm_init_(x, C, bias, logs, off=0, scale=1.0):
@@ -570,11 +545,10 @@ def actnorm_init_(x, C, bias, logs, off=0, scale=1.0):
     pitch = x.shape[-1]
     P = x.numel() // pitch
     lib = _lib.lib()
-    lib.glare_actnorm_init_workspace_bytes.restype = ctypes.c_size_t
-    nws = lib.glare_actnorm_init_workspace_bytes(_ll(P))
+    nws = lib.glare_actnorm_init_workspace_bytes(P)
     ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-    check(lib.glare_actnorm_init_f32(ptr(x), _i(pitch), _i(off), _i(C), _ll(P), _f(scale), ptr(bias), ptr(logs), ptr(ws),
-                                     ctypes.c_size_t(nws), stream_handle()), "glare_actnorm_init_f32")
+    check(lib.glare_actnorm_init_f32(ptr(x), pitch, off, C, P, scale, ptr(bias), ptr(logs), ptr(ws), nws,
+                                     stream_handle()), "glare_actnorm_init_f32")
 
 
 def flow_h1_raw(z, ftA, ftA_off, wz):
@@ -582,7 +556,7 @@ def flow_h1_raw(z, ftA, ftA_off, wz):
     require_cuda(z, ftA, wz)
     B, H, W, _ = z.shape
     out = torch.empty(B, H, W, 64, dtype=torch.float32, device=z.device)
-    check(_lib.lib().glare_flow_h1_raw_f32(ptr(z), ptr(ftA), _i(ftA.shape[3]), _i(ftA_off), ptr(wz), ptr(out), _i(B), _i(H), _i(W),
+    check(_lib.lib().glare_flow_h1_raw_f32(ptr(z), ptr(ftA), ftA.shape[3], ftA_off, ptr(wz), ptr(out), B, H, W,
                                            stream_handle()), "glare_flow_h1_raw_f32")
     return out
 
@@ -590,9 +564,8 @@ def flow_h1_raw(z, ftA, ftA_off, wz):
 def flow_affine3_(z, M, t):
     """z = M z + t in place (fp32 [.., 3]); M (9 floats, row-major) and t (3 floats) are host sequences."""
     require_cuda(z)
-    Ma = (ctypes.c_float * 9)(*[float(v) for v in M])
-    ta = (ctypes.c_float * 3)(*[float(v) for v in t])
-    check(_lib.lib().glare_flow_affine3_f32(ptr(z), _ll(z.numel() // 3), Ma, ta, stream_handle()), "glare_flow_affine3_f32")
+    Ma, ta = host_f32(M, 9), host_f32(t, 3)
+    check(_lib.lib().glare_flow_affine3_f32(ptr(z), z.numel() // 3, Ma, ta, stream_handle()), "glare_flow_affine3_f32")
     return z
 
 
@@ -602,7 +575,7 @@ def add_bf16(a, b, c=None):
     c = None if c is None else c.contiguous()
     assert a.dtype == b.dtype == act_dtype() and a.shape == b.shape
     out = torch.empty_like(a)
-    check(_lib.lib().glare_add_bf16(ptr(a), ptr(b), ptr(c), ptr(out), _ll(a.numel()), stream_handle()), "glare_add_bf16")
+    check(_lib.lib().glare_add_bf16(ptr(a), ptr(b), ptr(c), ptr(out), a.numel(), stream_handle()), "glare_add_bf16")
     return out
 
 
@@ -612,7 +585,7 @@ def colsum(g2d, C):
     assert g2d.dtype == act_dtype() and g2d.dim() == 2 and g2d.stride(1) == 1
     out = torch.empty(C, dtype=torch.float32, device=g2d.device)
     ws = torch.empty(256 * C, dtype=torch.float32, device=g2d.device)
-    check(_lib.lib().glare_colsum_bf16(ptr(g2d), _i(g2d.stride(0)), _ll(g2d.shape[0]), _i(C), ptr(out), ptr(ws), _sz(ws.numel() * 4),
+    check(_lib.lib().glare_colsum_bf16(ptr(g2d), g2d.stride(0), g2d.shape[0], C, ptr(out), ptr(ws), ws.numel() * 4,
                                        stream_handle()), "glare_colsum_bf16")
     return out
 
@@ -633,16 +606,15 @@ def conv_weight_grad_nhwc(ksize, x, g16, cout, cin=None, in_off=0, groups=1, x_g
     cin = pitch - in_off if cin is None else cin
     _count_flops("wgrad k%d" % ksize, 2.0 * groups * B * H * W * ksize * ksize * cin * cout)
     lib = _lib.lib()
-    lib.glare_conv_wgrad_workspace_bytes.restype = ctypes.c_size_t
-    nws = lib.glare_conv_wgrad_workspace_bytes(_i(ksize), _i(groups), _i(B), _i(H), _i(W), _i(cin), _i(cout))
+    nws = lib.glare_conv_wgrad_workspace_bytes(ksize, groups, B, H, W, cin, cout)
     if nws > WGRAD_MAX_WORKSPACE:     # the split count grows with the batch (one workgroup per image, strip and row range)
         raise _lib.GlareError("glare_conv_wgrad_bf16: %.1f GB of fp32 partials (limit %.1f GB)" % (nws / 2 ** 30, WGRAD_MAX_WORKSPACE / 2 ** 30))
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=x.device)
     if out is None:
         out = torch.empty(groups, ksize * ksize * cin + 1, cout, dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == groups * (ksize * ksize * cin + 1) * cout
-    check(lib.glare_conv_wgrad_bf16(_i(ksize), ptr(x), _i(pitch), _i(in_off), _ll(x_gstride), ptr(g16), _i(gpitch), _ll(g_gstride), ptr(out),
-                                    _i(groups), _i(B), _i(H), _i(W), _i(cin), _i(cout), ptr(ws), _sz(nws), stream_handle()),
+    check(lib.glare_conv_wgrad_bf16(ksize, ptr(x), pitch, in_off, x_gstride, ptr(g16), gpitch, g_gstride, ptr(out), groups, B, H, W, cin,
+                                    cout, ptr(ws), nws, stream_handle()),
           "glare_conv_wgrad_bf16")
     return out
 
@@ -656,13 +628,12 @@ def conv_weight_grad_oihw(ksize, x, g16, cout, dw, ci_off=0, db=None):
     B, H, W, cin = x.shape
     _count_flops("wgrad k%d" % ksize, 2.0 * B * H * W * ksize * ksize * cin * cout)
     lib = _lib.lib()
-    lib.glare_conv_wgrad_oihw_workspace_bytes.restype = ctypes.c_size_t
-    nws = lib.glare_conv_wgrad_oihw_workspace_bytes(_i(ksize), _i(B), _i(H), _i(W), _i(cin), _i(cout))
+    nws = lib.glare_conv_wgrad_oihw_workspace_bytes(ksize, B, H, W, cin, cout)
     if nws > WGRAD_MAX_WORKSPACE:
         raise _lib.GlareError("glare_conv_wgrad_oihw_bf16: %.1f GB of fp32 partials (limit %.1f GB)" % (nws / 2 ** 30, WGRAD_MAX_WORKSPACE / 2 ** 30))
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=x.device)
-    check(lib.glare_conv_wgrad_oihw_bf16(_i(ksize), ptr(x), _i(cin), _i(0), ptr(g16), _i(g16.shape[-1]), ptr(dw), _i(dw.shape[1]), _i(ci_off), ptr(db),
-                                         _i(B), _i(H), _i(W), _i(cin), _i(cout), ptr(ws), _sz(nws), stream_handle()), "glare_conv_wgrad_oihw_bf16")
+    check(lib.glare_conv_wgrad_oihw_bf16(ksize, ptr(x), cin, 0, ptr(g16), g16.shape[-1], ptr(dw), dw.shape[1], ci_off, ptr(db), B, H, W, cin,
+                                         cout, ptr(ws), nws, stream_handle()), "glare_conv_wgrad_oihw_bf16")
     return dw
 
 

@@ -1,5 +1,7 @@
 """CPU: the C-ABI library loads without a GPU and exports every symbol include/glare_hip.h
 declares; the product refuses CPU tensors instead of falling back."""
+import ast
+import ctypes
 import os
 import re
 import subprocess
@@ -8,6 +10,11 @@ import pytest
 import torch
 
 from glare_amd import _lib
+
+
+def _exports(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True).stdout
+    return set(re.findall(r"\bT (glare_[a-z0-9_]+)", out))
 
 
 def test_library_exports_every_declared_symbol():
@@ -37,10 +44,9 @@ def test_glare_error_carries_the_numeric_status():
 
 
 def test_no_extra_exports():
-    """Everything exported with the glare_ prefix is declared in the header (the ABI is the header)."""
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = set(re.findall(r"\bT (glare_[a-z0-9_]+)", out))
-    assert exported == set(_lib.header_symbols())
+    """Everything exported with the glare_ prefix is declared in the header (the ABI is the header), and the prototypes the binding
+    parses from it (header_symbols() is a view of signatures()) are exactly the exports."""
+    assert _exports(_lib.LIB_PATH) == set(_lib.header_symbols())
 
 
 def test_library_is_gfx950_only():
@@ -64,8 +70,7 @@ def test_half_library_exports_the_inference_entry_points():
     """libglare_hip_f16.so (IEEE-half activations / filters; since round 4 a build of EVERY source, training kernels included):
     each export is declared in the header -- a *_bf16 entry point under the name *_f16, identical signature -- and it exports
     nothing the header does not declare."""
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_F16_PATH], capture_output=True, text=True).stdout
-    exported = set(re.findall(r"\bT (glare_[a-z0-9_]+)", out))
+    exported = _exports(_lib.LIB_F16_PATH)
     declared = set(_lib.header_symbols())
     as_f16 = {n.replace("bf16", "f16") for n in declared}
     assert exported <= as_f16, sorted(exported - as_f16)
@@ -86,3 +91,102 @@ def test_half_library_exports_the_inference_entry_points():
         assert _lib.lib().glare_vq_nearest_f32 is not None       # dtype-agnostic: the main library's
     assert ops.act_dtype() == torch.bfloat16
     assert ops.inference_precision() == "fp16" and ops.inference_precision("bf16") == "bf16"
+
+
+def _assert_typed(fn, name):
+    restype, argtypes = _lib.signatures()[name]
+    assert fn.restype is restype, (name, fn.restype, restype)
+    assert fn.argtypes is not None and list(fn.argtypes) == argtypes, (name, fn.argtypes, argtypes)
+
+
+def test_every_entry_point_is_typed_from_the_header():
+    """Both libraries come out of lib() with argtypes / restype of every declared entry point set from its prototype: call sites pass
+    plain Python values, and no caller sets a type."""
+    lib = _lib.lib()
+    for name in _lib.header_symbols():
+        _assert_typed(getattr(lib, name), name)
+    half = {n.replace("bf16", "f16") for n in _exports(_lib.LIB_F16_PATH)}
+    with _lib.use_precision("fp16"):
+        lib16 = _lib.lib()
+        checked = 0
+        for name in _lib.header_symbols():
+            if name.replace("bf16", "f16") in half:
+                fn = getattr(lib16, name)
+                assert fn is getattr(lib16._c, name.replace("bf16", "f16"))       # the half library's export, typed as x_bf16
+                _assert_typed(fn, name)
+                checked += 1
+        assert checked == len(half)
+
+
+def test_header_parse_maps_the_closed_type_table_and_refuses_unknown_types():
+    c = ctypes
+    sigs = _lib.parse_prototypes("""
+        #define GLARE_PAD_SYMMETRIC 1   /* a define right above a prototype */
+        int glare_pad(const unsigned char* x, int mode, glare_stream_t stream);
+        typedef struct glare_thing { int a; float* b; } glare_thing;
+        const char* glare_name(int status);   // trailing comment
+        size_t glare_bytes(int B,
+                           long long HW);
+        long long glare_count(void);
+        int glare_fill(const glare_thing* t, float v, const float* M_3x3_host, double* out);""")
+    assert sigs == {"glare_pad": (c.c_int, [c.c_void_p, c.c_int, c.c_void_p]),
+                    "glare_name": (c.c_char_p, [c.c_int]),
+                    "glare_bytes": (c.c_size_t, [c.c_int, c.c_longlong]),
+                    "glare_count": (c.c_longlong, []),
+                    "glare_fill": (c.c_int, [c.c_void_p, c.c_float, c.c_void_p, c.c_void_p])}
+    for bad in ("int glare_x(double v);", "int glare_x(unsigned n);", "double glare_x(int n);", "int glare_x(int);"):
+        with pytest.raises(_lib.GlareError):
+            _lib.parse_prototypes(bad)
+
+
+_SCALAR_CTYPE = re.compile(r"c_(u?(byte|short|int|long|longlong)\d*|size_t|ssize_t|float|double|longdouble|bool)$")
+
+
+def test_call_sites_pass_the_declared_number_of_arguments():
+    """A static audit of every literal `.glare_<name>(...)` call: ctypes accepts EXTRA arguments to a typed cdecl function silently,
+    so this is what catches one.  Outside glare_amd/_lib.py nothing sets a restype / argtypes, constructs a scalar ctypes value
+    or aliases a scalar ctypes type -- the header's prototypes are the only binding."""
+    sigs = _lib.signatures()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    files = [os.path.join(d, f) for sub in ("glare_amd", "tests", "tools") for d, _, fs in os.walk(os.path.join(root, sub))
+             for f in fs if f.endswith(".py")]
+    lib_py = os.path.join(root, "glare_amd", "_lib.py")
+    calls, bad = 0, []
+    for path in files:
+        where = os.path.relpath(path, root)
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith("glare_"):
+                if any(isinstance(a, ast.Starred) for a in node.args) or node.keywords:
+                    continue
+                name = node.func.attr
+                if name not in sigs:
+                    bad.append("%s:%d calls %s, which the header does not declare" % (where, node.lineno, name))
+                elif len(node.args) != len(sigs[name][1]):
+                    bad.append("%s:%d passes %d arguments to %s (declared: %d)" % (where, node.lineno, len(node.args), name, len(sigs[name][1])))
+                calls += 1
+            if path == lib_py:
+                continue
+            if isinstance(node, (ast.Assign, ast.AugAssign, ast.AnnAssign)):
+                targets = node.targets if isinstance(node, ast.Assign) else [node.target]
+                if any(isinstance(t, ast.Attribute) and t.attr in ("restype", "argtypes") for t in targets):
+                    bad.append("%s:%d sets a restype / argtypes" % (where, node.lineno))
+                v = node.value
+                if isinstance(v, ast.Attribute) and _SCALAR_CTYPE.match(v.attr):
+                    bad.append("%s:%d aliases ctypes.%s" % (where, node.lineno, v.attr))
+                if isinstance(v, ast.Tuple) and any(isinstance(e, ast.Attribute) and _SCALAR_CTYPE.match(e.attr) for e in v.elts):
+                    bad.append("%s:%d aliases a scalar ctypes type" % (where, node.lineno))
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and _SCALAR_CTYPE.match(node.func.attr):
+                bad.append("%s:%d constructs ctypes.%s" % (where, node.lineno, node.func.attr))
+            if isinstance(node, ast.ImportFrom) and node.module == "ctypes" and any(_SCALAR_CTYPE.match(a.name) for a in node.names):
+                bad.append("%s:%d imports a scalar ctypes type" % (where, node.lineno))
+    assert calls > 150
+    assert not bad, "\n".join(bad)
+
+
+def test_size_queries_return_their_full_width_without_caller_types():
+    """A size_t / long long result past 2^32 comes back whole with no restype set by the caller (host-only queries: no GPU needed)."""
+    lib = _lib.lib()
+    one = lib.glare_groupnorm_workspace_bytes(1, 64)
+    assert one > 0 and lib.glare_groupnorm_workspace_bytes(2 ** 30, 64) == 2 ** 30 * one > 2 ** 32
+    # glare_hip.h: [wz hi | lo] 2 x 2 KB, [W2 hi | lo] 2 x 8 KB, [W4 hi | lo] 2 x 8 KB, fp32 b2 [2][2][16] and b4[4]
+    assert lib.glare_flow_step_fused_image_bytes() == 2 * 2048 + 4 * 8192 + 4 * (2 * 2 * 16 + 4)

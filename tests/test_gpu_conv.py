@@ -252,8 +252,6 @@ def test_conv_randomised_shapes_and_fusions():
 def test_error_behaviour_of_the_new_entry_points():
     """Status codes instead of crashes: CPU tensors are refused before any launch, a sub-pixel filter cannot serve a plain
     conv, the sub-pixel form exists for stride 1 only, and the fused add refuses shapes its statistics pass cannot tile."""
-    import ctypes
-
     from glare_amd import _lib
 
     w = torch.randn(64, 64, 3, 3) * 0.02
@@ -271,10 +269,8 @@ def test_error_behaviour_of_the_new_entry_points():
     with pytest.raises(_lib.GlareError, match="unsupported"):
         ops.add_bf16(a, a, gn_stats=True)
     lib = _lib.lib()
-    lib.glare_conv2d_upsample_packed_weight_elems.restype = ctypes.c_longlong
-    assert lib.glare_conv2d_upsample_packed_weight_elems(ctypes.c_int(0), ctypes.c_int(64)) < 0
-    assert lib.glare_add_groupnorm_stats_bf16(None, None, None, ctypes.c_int(1), ctypes.c_longlong(16), ctypes.c_int(64), None,
-                                              ctypes.c_size_t(0), None) != 0
+    assert lib.glare_conv2d_upsample_packed_weight_elems(0, 64) < 0
+    assert lib.glare_add_groupnorm_stats_bf16(None, None, None, 1, 16, 64, None, 0, None) != 0
 
 
 # ---- 1x1 convolution, weight-stationary kernel (csrc/conv1x1.hip) ----------------------------------------------------------
@@ -348,7 +344,6 @@ def test_narrower_output_channel_tiles_give_the_same_bits(B, Cin, Cout, H, W, k,
     assignment of output channels to workgroups changes, every output's contraction order is the same, so the results are bit-equal;
     glare_conv2d_cout_tile picks the default for the BASELINE shapes and a narrower tile for the training crops."""
     from glare_amd import _lib
-    import ctypes
 
     g = torch.Generator().manual_seed(B + Cin + Cout)
     x = _nhwc_bf16(_rand((B, Cin, H, W), g))
@@ -362,10 +357,9 @@ def test_narrower_output_channel_tiles_give_the_same_bits(B, Cin, Cout, H, W, k,
         got = ops.conv2d(x, pc, stride=stride, upsample=ups, act="relu" if r is None else "none", residual=r)
         assert torch.equal(got, ref)
     pick = _lib.lib().glare_conv2d_cout_tile
-    i = ctypes.c_int
-    assert pick(i(8), i(420), i(620), i(128)) == 128 and pick(i(8), i(105), i(155), i(512)) == 128       # the BASELINE batch: default
-    assert pick(i(1), i(256), i(256), i(128)) == 64 and pick(i(1), i(64), i(64), i(512)) == 32          # stage-3 crop
-    assert pick(i(2), i(80), i(80), i(512)) == 64 and pick(i(2), i(80), i(80), i(64)) == 64 and pick(i(1), i(8), i(8), i(16)) == 32
+    assert pick(8, 420, 620, 128) == 128 and pick(8, 105, 155, 512) == 128       # the BASELINE batch: default
+    assert pick(1, 256, 256, 128) == 64 and pick(1, 64, 64, 512) == 32          # stage-3 crop
+    assert pick(2, 80, 80, 512) == 64 and pick(2, 80, 80, 64) == 64 and pick(1, 8, 8, 16) == 32
     # fused GroupNorm statistics: the 64-wide tile keeps the 4-row wave slabs of the 128-wide one (same sums, another fp32 order);
     # the 32-wide tile's waves cover 2 rows each and are refused
     xs, ws = _nhwc_bf16(_rand((1, 128, 16, 32), g)), _rand((128, 128, 3, 3), g).cuda()

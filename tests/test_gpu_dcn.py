@@ -289,8 +289,6 @@ def test_general_shapes_forward_and_backward_match_c_oracle(B, C, H, W, Co, k, s
 
 
 def test_general_shapes_c_abi_needs_no_workspace_and_rejects_bad_channel_counts():
-    import ctypes
-
     from glare_amd import _lib
 
     lib = _lib.lib()
@@ -299,10 +297,8 @@ def test_general_shapes_c_abi_needs_no_workspace_and_rejects_bad_channel_counts(
     x, off, m = torch.randn(B, C, H, W, generator=g).cuda(), torch.randn(B, dg * 18, H, W, generator=g).cuda(), torch.rand(B, dg * 9, H, W, generator=g).cuda()
     w = torch.randn(Co, C, 3, 3, generator=g).cuda()
     out = torch.empty(B, Co, H, W, device="cuda")
-    i = ctypes.c_int
-    args = lambda c, groups, dgs: (_lib.ptr(x), _lib.ptr(off), _lib.ptr(m), _lib.ptr(w), ctypes.c_void_p(0), _lib.ptr(out), i(B), i(c), i(H),
-                                   i(W), i(Co), i(3), i(3), i(1), i(1), i(1), i(1), i(1), i(1), i(groups), i(dgs), ctypes.c_void_p(0),
-                                   ctypes.c_size_t(0), _lib.stream_handle())
+    args = lambda c, groups, dgs: (_lib.ptr(x), _lib.ptr(off), _lib.ptr(m), _lib.ptr(w), None, _lib.ptr(out), B, c, H, W, Co, 3, 3,
+                                   1, 1, 1, 1, 1, 1, groups, dgs, None, 0, _lib.stream_handle())
     assert lib.glare_mdcn_forward_f32(*args(C, 1, dg)) == 0                 # NULL workspace: the general kernels need none
     ref = c_ref.dcn_forward(x.cpu().numpy(), off.cpu().numpy(), m.cpu().numpy(), w.cpu().numpy(), None, dg=dg)
     _close(out.cpu().numpy(), ref)

@@ -1,6 +1,5 @@
 """3x3 convs whose launch does not fill the chip (training crops, batch 1): the default 128-wide output-channel tile against
 64 / 32 (glare_conv_desc.cout_tile) and what glare_conv2d_cout_tile picks."""
-import ctypes
 import os
 import sys
 
@@ -35,6 +34,5 @@ for name, B, H, W, ci, co in [("128->128 @256 B1", 1, 256, 256, 128, 128), ("256
     for tile in (0, 64, 32):
         pc = ops.PackedConv(w, bias, cout_tile=tile)
         res.append(2.0 * B * H * W * 9 * ci * co / timeit(lambda: ops.conv2d(x, pc)) / 1e9)
-    i = ctypes.c_int
-    pick = _lib.lib().glare_conv2d_cout_tile(i(B), i(H), i(W), i(co))
+    pick = _lib.lib().glare_conv2d_cout_tile(B, H, W, co)
     print("conv %-18s TFLOP/s with the 128 / 64 / 32 tile: %4.0f / %4.0f / %4.0f   picked: %d" % (name, *res, pick))
