@@ -11,9 +11,12 @@ the timed region starts.  Images are independent, so N GPUs shard the batch with
 collective (weak scaling: 8 images per GPU); at N > 1 every step ends with the one exchange the inference
 path has -- the RCCL gather of the enhanced images to rank 0 (BASELINE configs[2]) -- plus the timing
 barrier / max.  Started as a plain process with --gpus N > 1, bench.py launches the N ranks itself.
-Rank 0 prints ONE JSON line, including
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints it.  With --full
+the same run goes on behind the timed region and the line also carries
   roofline     -- the dominant kernel (d=512 blockwise attention, shared keys / values) measured live with
                   events on the launch stream, against the dense bf16 MFMA peak;
+  rooflines, value_single_stream, power, train -- the other kernel families, the single-stream rate, the clock /
+                  power annotation and the stage-2 / stage-3 training steps;
   cpu_baseline -- the CPU oracle (a port of the reference's fp32 torch path) timed on this box's host
                   cores on one 400x600 image.
 """
@@ -531,12 +534,18 @@ def main():
                     help="16-bit format of activations and filters: fp16 (default: IEEE half, the reference's own autocast dtype and "
                          "the precision the end-to-end tolerance is met in; libglare_hip_f16.so) or bf16 (libglare_hip.so, +2.7 %% "
                          "images/s, 8x the rounding per stored tensor).  The JSON line's `dtype` names what ran")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-power", action="store_true", help="skip the clock / power annotation (`power`: 5 s after the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region, also measure what the headline does not need: the single-stream region and the "
+                         "rooflines (`value_single_stream`, `roofline`, `rooflines`), the clock / power annotation (`power`), the "
+                         "training steps (`train`) and the CPU baseline (`cpu_baseline`, `reference_on_mi355x`).  Off: those keys are null "
+                         "or absent.  The --no-* options below skip one of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-power", action="store_true", help="with --full: skip the clock / power annotation (`power`: 5 s after the timed region)")
     ap.add_argument("--no-single-stream", "--no-streams2", dest="no_single_stream", action="store_true",
-                    help="with --streams > 1: skip the single-stream region behind the timed one (the roofline then comes from isolated launches)")
-    ap.add_argument("--no-train", action="store_true", help="skip the `train` block (stage-2 / stage-3 ms per step, measured after "
-                                                            "the inference region)")
+                    help="with --full and --streams > 1: skip the single-stream region behind the timed one (the roofline then comes from "
+                         "isolated launches)")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the `train` block (stage-2 / stage-3 ms per step, measured "
+                                                            "after the inference region)")
     ap.add_argument("--train-timeout", type=int, default=600, help="seconds after which a train block that has not returned is "
                                                                    "declared hung: the JSON line is printed without it")
     ap.add_argument("--dist-timeout", type=int, default=300, help="N > 1: seconds any one stage of the multi-rank body (init, first collective, "
@@ -687,6 +696,7 @@ def main():
         device_sync()
         timed_steps(step, 0, args.warmup, dist, dog)          # the W untimed warm-up steps (+ barrier)
         single = streams is None
+        # armed without --full too, so that the timed steps are the same launches with and without it
         if rank == 0 and not STUB and single:
             ops.ATTENTION_LAUNCH_EVENTS = []     # roofline: the dominant kernel's launches are timed where they run
             ops.LAUNCH_EVENTS = {"conv3x3": [], "conv3x3_split": [], "dcn": []}     # ... and the next families (`rooflines`)
@@ -711,7 +721,7 @@ def main():
         dog.cancel()
 
     value_single_stream = None
-    if not single and rank == 0 and not STUB and not args.no_single_stream:
+    if args.full and not single and rank == 0 and not STUB and not args.no_single_stream:
         # The same K steps once more on ONE stream, rank 0 only, no collective (at N > 1 the other ranks wait at the next barrier): a
         # launch that shares the GPU with the other stream's kernels has no duration of its own, so the roofline's event pairs are taken
         # here -- same pipeline, same data, launches back to back.  Reported beside `value` (`value_single_stream`: rounds 1-5's headline).
@@ -760,13 +770,14 @@ def main():
                                     "(12 scenes: index agreement >= 0.9992, |dPSNR vs GT| <= 0.005 dB; tests/test_gpu_precision.py).  Cost "
                                     "against round 3's single-pass fp16 path: -19 % images/s.  bf16 (BASELINE configs[1]'s literal dtype) "
                                     "misses the tolerance by 10x (0.53 dB, 0.48 index agreement) and is offered as --precision bf16 only"},
+            "full": args.full,
             "value_single_stream": value_single_stream,
-            "roofline": None if STUB else attention_roofline(device, args.batch, live_events),
-            "rooflines": None if STUB else family_rooflines(family_events, args.steps),
+            "roofline": attention_roofline(device, args.batch, live_events) if args.full and not STUB else None,
+            "rooflines": family_rooflines(family_events, args.steps) if args.full and not STUB else None,
             "power": None,
             "train": None,
         }
-        if not STUB and world == 1 and not args.no_power:
+        if args.full and not STUB and world == 1 and not args.no_power:
             try:
                 res["power"] = power_block(device, args.batch, step_single)
             except Exception as ex:      # telemetry is an annotation: it must never cost the line
@@ -774,7 +785,7 @@ def main():
         if STUB:
             res["stub"] = True
 
-    if not args.no_train:
+    if args.full and not args.no_train:
         # After the timed inference region, and never allowed to take the headline line down with it: an exception is reported
         # inside the block, and -- the all-reduce leg has only ever run under gloo on CPU before a driver's N > 1 run -- a HANG
         # is cut by a watchdog on rank 0 that prints the line with what it has and ends the job (torchrun then stops the others).
@@ -798,7 +809,7 @@ def main():
         if res is not None:
             res["train"] = train
 
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and not STUB:  # reported at N = 1 only
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1 and not STUB:  # reported at N = 1 only
         res["cpu_baseline"] = cpu_baseline()
         # NOT measured by this run (bench.py executes nothing under oracle/ outside cpu_baseline): a citation of the committed GPU-side
         # measurement of the reference's own path on this hardware, beside the CPU figure above

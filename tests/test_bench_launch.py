@@ -61,7 +61,7 @@ def test_bench_world_2_skeleton_runs_over_gloo(literal):
     """literal: BASELINE configs[2] as written -- a GLOBAL batch split over the ranks (`--global-batch`, strong scaling) instead of
     `--batch` images per GPU at every N.
     VERDICT r03: bench.py's own world > 1 body -- process-group init, the per-step RankGather inside the timed region, the barrier
-    / synchronize brackets, the max over ranks, the train block's per-group all-reduce (early + blocking) -- executed for real by two
+    / synchronize brackets, the max over ranks, the train block's per-group all-reduce (early + blocking, --full) -- executed for real by two
     ranks, on CPU over gloo, with the HIP pipeline replaced by tensor stand-ins (GLARE_BENCH_STUB=1).  Started as a plain process,
     so the self-launch is part of it."""
     import json
@@ -70,7 +70,7 @@ def test_bench_world_2_skeleton_runs_over_gloo(literal):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     shape = ["--global-batch", "4"] if literal else ["--batch", "2"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"] + shape,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1"] + shape,
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -86,20 +86,33 @@ def test_bench_world_2_skeleton_runs_over_gloo(literal):
 
 def test_bench_prints_its_line_when_the_train_block_hangs():
     """The all-reduce leg of the train block has never run on more than one GPU: if it ever hangs there, the headline line must
-    still come out.  A stub trainer that never returns (GLARE_BENCH_STUB_HANG=1) under `--train-timeout 3`: rank 0's watchdog prints
+    still come out.  A stub trainer that never returns (GLARE_BENCH_STUB_HANG=1) under `--full --train-timeout 3`: rank 0's watchdog prints
     the inference line with the error recorded in `train` and ends the process."""
     import json
 
     env = dict(os.environ, GLARE_BENCH_STUB="1", GLARE_BENCH_STUB_HANG="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--train-timeout", "3"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "2",
+                        "--train-timeout", "3"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     res = json.loads(lines[0])
     assert res["value"] > 0 and "did not finish" in res["train"]["error"]
+
+
+def test_bench_plain_run_stops_at_the_headline():
+    """Without --full the run ends with the headline line: the stub trainer that never returns (GLARE_BENCH_STUB_HANG=1) is not
+    reached, no watchdog fires, and every key measured behind the timed region is null."""
+    r, lines = _run_bench_stub(["--steps", "2", "--warmup", "1", "--batch", "2"], {"GLARE_BENCH_STUB_HANG": "1"}, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(lines) == 1
+    res = lines[0]
+    assert res["full"] is False and res["value"] > 0 and res["steps"] == 2 and res["warmup"] == 1
+    assert res["train"] is None and res["power"] is None and res["roofline"] is None and res["rooflines"] is None
+    assert res["value_single_stream"] is None and "cpu_baseline" not in res
 
 
 def _run_bench_stub(args, extra_env=None, timeout=900):
