@@ -9,6 +9,7 @@ Every entry point is typed once, at load, from its prototype in the header (sign
 numbers, ptr() of a tensor and stream_handle(), and never set a restype or argtypes themselves.
 """
 import ctypes
+import keyword
 import os
 import re
 import threading
@@ -43,9 +44,6 @@ class GlareError(RuntimeError):
         self.status = status
 
 
-ERR_INVALID, ERR_LAUNCH, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -3, -4     # include/glare_hip.h:37-40
-
-
 # The closed table of C types the ABI uses: any pointer (and glare_stream_t) is a void*; anything else raises.
 _SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
 
@@ -61,11 +59,15 @@ def _ctype(decl, is_return=False):
     raise GlareError("no ctypes binding for the C type %r (glare_amd/_lib.py _SCALARS)" % decl)
 
 
+def _strip(text, preprocessor=True):
+    """C header text without its comments and (unless preprocessor=False) without its preprocessor lines."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    return re.sub(r"^\s*#.*$", " ", text, flags=re.M) if preprocessor else text      # `#define GLARE_PAD_SYMMETRIC 1` must not glue onto the next return type
+
+
 def parse_prototypes(text):
     """{name: (restype, [argtypes])} of every glare_* function prototype in C header text."""
-    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)      # `#define GLARE_PAD_SYMMETRIC 1` must not glue onto the next return type
-    text = re.sub(r"\{[^{}]*\}", " ", text.replace('extern "C" {', " "))     # struct / enum bodies
+    text = re.sub(r"\{[^{}]*\}", " ", _strip(text).replace('extern "C" {', " "))     # struct / enum bodies
     sigs = {}
     for stmt in text.split(";"):
         m = re.fullmatch(r"\s*(.*?)\b(glare_\w+)\s*\((.*)\)\s*", stmt, flags=re.S)
@@ -84,16 +86,60 @@ def parse_prototypes(text):
     return sigs
 
 
-_SIGNATURES = None
+def parse_structs(text):
+    """{name: ctypes.Structure subclass} of every `typedef struct glare_X { ... } glare_X;` in C header text: fields in the header's
+    order and of the closed type table; `int B, H, W;` declares three; a field named like a Python keyword gets a trailing underscore."""
+    structs = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(glare_\w+)\s*\{(.*?)\}\s*\1\s*;", _strip(text), flags=re.S):
+        if "{" in body or "}" in body:
+            raise GlareError("%s: nested struct / union / enum bodies are not supported" % name)
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            first, *more = [p.strip() for p in decl.split(",")]
+            m = re.fullmatch(r"(.+?)\s*\b(\w+)", first)
+            if m is None or not all(re.fullmatch(r"\w+", p) for p in more):      # arrays, bit fields, `*b` after a comma, ...
+                raise GlareError("%s: cannot parse the field declaration %r" % (name, decl))
+            ctype = _ctype(m.group(1))
+            fields += [(f + "_" if keyword.iskeyword(f) else f, ctype) for f in [m.group(2)] + more]
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": "`%s` of include/glare_hip.h." % name})
+    return structs
+
+
+def parse_constants(text):
+    """{name: int} of every `#define GLARE_<NAME> <integer>` / `(<integer>)` and every `GLARE_<NAME> = <integer>` of an enum in C header text."""
+    text = _strip(text, preprocessor=False)
+    consts = {n: int(v) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(GLARE_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    for body in re.findall(r"\benum\s*\{([^{}]*)\}", text):
+        consts.update((n, int(v)) for n, v in re.findall(r"\b(GLARE_\w+)\s*=\s*(-?\d+)\s*(?:,|$)", body))
+    return consts
+
+
+_PARSED = {}
+
+
+def _header(parser):
+    if parser not in _PARSED:
+        with open(HEADER_PATH) as f:
+            _PARSED[parser] = parser(f.read())
+    return _PARSED[parser]
 
 
 def signatures():
     """{name: (restype, [argtypes])} of every function declared in include/glare_hip.h (parsed once)."""
-    global _SIGNATURES
-    if _SIGNATURES is None:
-        with open(HEADER_PATH) as f:
-            _SIGNATURES = parse_prototypes(f.read())
-    return _SIGNATURES
+    return _header(parse_prototypes)
+
+
+def structs():
+    """{name: ctypes.Structure subclass} of every struct declared in include/glare_hip.h (parsed once)."""
+    return _header(parse_structs)
+
+
+def constants():
+    """{name: int} of every integer GLARE_* constant of include/glare_hip.h (parsed once)."""
+    return _header(parse_constants)
+
+
+ERR_INVALID, ERR_LAUNCH, ERR_WORKSPACE, ERR_UNSUPPORTED = (constants()["GLARE_ERR_" + n] for n in ("INVALID", "LAUNCH", "WORKSPACE", "UNSUPPORTED"))
 
 
 def header_symbols():

@@ -9,14 +9,14 @@ import math
 import numpy as np
 import torch
 
+from . import _lib
+
 PAD = 20
 
 
 # ---- device versions (csrc/harness.hip): batched, uint8 in, PSNR out ------------------------------------------
 def preprocess_device(imgs_u8):
     """uint8 device tensor [B,H,W,3] -> fp32 [B,3,H+20,W+20] in the log domain (same arithmetic as preprocess())."""
-    from . import _lib
-
     _lib.require_cuda(imgs_u8)
     assert imgs_u8.dtype == torch.uint8 and imgs_u8.dim() == 4 and imgs_u8.shape[3] == 3 and imgs_u8.is_contiguous()
     B, H, W, _ = imgs_u8.shape
@@ -30,8 +30,6 @@ def postprocess_device(out_nchw, h, w, gts_u8=None, want_nonfinite=False):
     """network output [B,3,Hp,Wp] (device) -> (restored float [B,h,w,3], psnr float64 [B] or None), all on the device.
     want_nonfinite: a third result, int32 [B] = inf / NaN values of the network output inside each crop BEFORE the clamp (which maps
     +inf to 1.0 and would hide an fp16 overflow behind a finite PSNR)."""
-    from . import _lib
-
     _lib.require_cuda(out_nchw, gts_u8)
     out_nchw = out_nchw.float().contiguous()
     B, _, Hp, Wp = out_nchw.shape
@@ -54,8 +52,6 @@ def postprocess_device(out_nchw, h, w, gts_u8=None, want_nonfinite=False):
 
 def to_ubyte_device(restored):
     """restored float [..] in [0,1] (device) -> uint8 of the same shape: img_as_ubyte, the image the reference's loop saves."""
-    from . import _lib
-
     _lib.require_cuda(restored)
     restored = restored.float().contiguous()
     out = torch.empty(restored.shape, dtype=torch.uint8, device=restored.device)
@@ -68,7 +64,6 @@ def ssim_device(restored, gts_u8):
     """SSIM as the reference's evaluation loop computes it (calculate_ssim(img_as_ubyte(target), img_as_ubyte(restored)),
     utils2.py:42-89 / infer_dataset_lol.py:152): restored float [B,h,w,3] in [0,1] and the uint8 ground truth, both on the device
     -> float64 [B] (device).  11x11 Gaussian (sigma 1.5) window at the valid positions, per channel, averaged."""
-    from . import _lib
     from . import train_ops as T
 
     _lib.require_cuda(restored, gts_u8)
@@ -86,7 +81,7 @@ def ssim_device(restored, gts_u8):
 
 
 # ---- unpaired enhancement (code/infer_unpaired.py:81-136): any size, no GT, uint8 out --------------------------------
-PAD_REFLECT101, PAD_SYMMETRIC = 0, 1        # GLARE_PAD_* of include/glare_hip.h
+PAD_REFLECT101, PAD_SYMMETRIC = (_lib.constants()["GLARE_PAD_" + n] for n in ("REFLECT101", "SYMMETRIC"))     # include/glare_hip.h
 
 
 def auto_padding(h, w, times=16):
@@ -99,8 +94,6 @@ def auto_padding(h, w, times=16):
 def preprocess_unpaired_device(imgs_u8, pads=None, mode=PAD_SYMMETRIC):
     """uint8 device tensor [B,H,W,3] -> fp32 [B,3,Hp,Wp] in the log domain, padded by `pads` = (top, bottom, left, right)
     (default auto_padding) with cv2.BORDER_REFLECT (mode PAD_SYMMETRIC) or numpy 'reflect' (PAD_REFLECT101)."""
-    from . import _lib
-
     _lib.require_cuda(imgs_u8)
     assert imgs_u8.dtype == torch.uint8 and imgs_u8.dim() == 4 and imgs_u8.shape[3] == 3 and imgs_u8.is_contiguous()
     B, H, W, _ = imgs_u8.shape
@@ -115,8 +108,6 @@ def postprocess_unpaired_device(out_nchw, pads, h, w, want_nonfinite=False):
     """network output [B,3,Hp,Wp] (device) -> uint8 [B,h,w,3] (device): the window at (pads[0], pads[2]), clamped and TRUNCATED to
     uint8 as rgb() does (infer_unpaired.py:42, :129-130).  want_nonfinite: also int32 [B], the inf / NaN values of each window
     before the clamp (the overflow flag of glare_amd.infer)."""
-    from . import _lib
-
     _lib.require_cuda(out_nchw)
     out_nchw = out_nchw.float().contiguous()
     B, _, Hp, Wp = out_nchw.shape

@@ -26,24 +26,11 @@ def vq_nearest(z_tokens, codebook, want_zq=True):
 
 
 # ---- convolution --------------------------------------------------------------------------------
-ACT = {"none": 0, "relu": 1, "sigmoid": 2, "swish": 3}
-OUT_NHWC_BF16, OUT_NHWC_F32, OUT_PLANAR_F32, OUT_PLANAR_BF16 = 0, 1, 2, 3
-
-
-class ConvDesc(ctypes.Structure):
-    """Mirror of `glare_conv_desc` (include/glare_hip.h)."""
-    _fields_ = [("in_", ctypes.c_void_p), ("in2", ctypes.c_void_p), ("weight_packed", ctypes.c_void_p),
-                ("bias", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("Cin", ctypes.c_int), ("in_pitch", ctypes.c_int), ("in_off", ctypes.c_int),
-                ("Cin2", ctypes.c_int), ("in2_pitch", ctypes.c_int), ("in2_off", ctypes.c_int),
-                ("Cout", ctypes.c_int), ("out_pitch", ctypes.c_int), ("out_off", ctypes.c_int),
-                ("res_pitch", ctypes.c_int), ("res_off", ctypes.c_int),
-                ("ksize", ctypes.c_int), ("stride", ctypes.c_int), ("upsample", ctypes.c_int), ("act", ctypes.c_int), ("out_mode", ctypes.c_int),
-                ("plane_pitch", ctypes.c_longlong), ("gn_partial", ctypes.c_void_p), ("cout_tile", ctypes.c_int),
-                ("residual_lo", ctypes.c_void_p), ("out_lo", ctypes.c_void_p),
-                ("groups", ctypes.c_int), ("group_in_step", ctypes.c_int), ("group_out_step", ctypes.c_int), ("k_wrap", ctypes.c_int),
-                ("gn_coef", ctypes.c_void_p), ("gn_swish", ctypes.c_int)]
+# Every constant and both structs of this section are read from include/glare_hip.h (_lib.constants(), _lib.structs()).
+_K = _lib.constants()
+ACT = {name: _K["GLARE_ACT_" + name.upper()] for name in ("none", "relu", "sigmoid", "swish")}
+OUT_NHWC_BF16, OUT_NHWC_F32, OUT_PLANAR_F32, OUT_PLANAR_BF16 = (_K["GLARE_OUT_" + n] for n in ("NHWC_BF16", "NHWC_F32", "PLANAR_F32", "PLANAR_BF16"))
+ConvDesc = _lib.structs()["glare_conv_desc"]          # the field `in` is `in_` here
 
 
 # k_wrap = 2 (round 5): the K order of an fp32-class 3x3 conv in which every x_hi halo tile is staged ONCE for the two filter halves it
@@ -96,102 +83,148 @@ def filter_feedback_round(w):
     return out
 
 
-class PackedConv:
-    """A conv filter packed once for the MFMA kernel (weights bf16 stage-ordered, bias fp32)."""
+def split_k_wrap(split, w):
+    """glare_conv_desc.k_wrap of a filter [..., cout, cin, k, k] packed with `split` K segments: 0 = plain, 2 = the order that stages
+    x_hi once (SPLIT_A_REUSE; split-3 3x3 filters whose cin fills whole 16-channel stages), 1 = the segment order otherwise."""
+    if not split:
+        return 0
+    return 2 if (split == 3 and SPLIT_A_REUSE and w.shape[-1] == 3 and w.shape[-3] % 16 == 0) else 1
 
-    def __init__(self, weight_oihw, bias=None, dgrad_pad=None, upsample_subpixel=False, cout_tile=0, split=0, feedback=False):
+
+def _f32(t):
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _ws_image(w, cout, cin):
+    """The plain 16-bit [Cout][Cin] image of an fp32 1x1 filter that the weight-stationary kernel (csrc/conv1x1.hip) reads."""
+    w16 = torch.empty(cout, cin, dtype=act_dtype(), device=w.device)
+    check(_lib.lib().glare_conv1x1_ws_pack_weight(ptr(w), cout, cin, ptr(w16), stream_handle()), "glare_conv1x1_ws_pack_weight")
+    return w16
+
+
+class PackedConv:
+    """A conv filter packed once for the MFMA kernels.  Every instance has every field; _set() is the one place that assigns them:
+    ksize, cout, cin   of the conv as launched (a dgrad pack: cout = the forward conv's cin, cin = dgrad_pad; a split pack: cin = the
+                       conv's own input channels, the packed image holds `split` K segments of them)
+    packed             the stage-ordered 16-bit image (glare_conv_desc.weight_packed);  bias: fp32 [cout] or None
+    split, k_wrap      0 / 0, or the fp32-class form: 2 or 3 K segments in the order split_k_wrap() chose
+    subpixel, cout_tile  what __init__ was asked for (a sub-pixel pack has no tile: 0)
+    w16, w16_lo        plain [Cout][Cin] images for the weight-stationary 1x1 kernel (w16_lo: the lo half of a split-3 filter), or None
+    _src, _tiles       (fp32 filter, bias, dgrad_pad) for AUTO_COUT_TILE's re-packs and the re-packs made so far ({tile: PackedConv})
+    _param             the parameter a PackCache entry is re-packed from (PackCache.get sets it), else None"""
+    __slots__ = ("ksize", "cout", "cin", "packed", "bias", "split", "k_wrap", "subpixel", "cout_tile", "w16", "w16_lo", "_src", "_tiles", "_param")
+
+    def __init__(self, weight_oihw=None, bias=None, dgrad_pad=None, upsample_subpixel=False, cout_tile=0, split=0, feedback=False, *, _fields=None):
         """dgrad_pad = P: pack the filter of the data-gradient conv (P >= cout input channels, cin outputs) instead.
         cout_tile: 0 = the default output-channel tile for this cout, or 64 / 32 for launches too small to fill the chip with it
         (conv_cout_tile(); the packed image is tile-specific and conv2d passes the tile on).
         upsample_subpixel: pack the four 2x2 sub-pixel filters of "nearest x2 upsample, then this 3x3 conv" (conv2d then runs
         desc.upsample = 2: 16 instead of 36 tap-MACs per source pixel); feedback (with it): round the four phase filters with error
-        feedback per output channel (filter_feedback_round; plain filters are fed pre-rounded by modules._base.packed_conv)."""
+        feedback per output channel (filter_feedback_round; plain filters are fed pre-rounded by modules._base.packed_conv).
+        split: the fp32-class form -- conv2d() reads the activation's hi / lo pair against [w_hi | w_hi | w_lo].
+        _fields: packed_conv_batch's "filter k of a batched pack" -- the fields as they are."""
+        if _fields is not None:
+            self._set(**_fields)
+            return
         require_cuda(weight_oihw)
         w = weight_oihw.detach().float().contiguous()
-        self.split = int(split)
-        self.k_wrap = 1 if split else 0
-        if split:       # the fp32-class form: conv2d() reads the activation's hi / lo pair against [w_hi | w_hi | w_lo]
-            assert dgrad_pad is None and not upsample_subpixel and not cout_tile
-            if split == 3 and SPLIT_A_REUSE and w.shape[-1] == 3 and w.shape[1] % 16 == 0:
-                self.k_wrap = 2
-                w = split_filter(w, split, reuse_kc=16)
-            else:
-                w = split_filter(w, split)
-        cout, cin, kh, kw = w.shape
-        assert kh == kw and kh in (1, 3)
-        self.ksize = kh
-        self.subpixel = bool(upsample_subpixel)
-        self.cout_tile = 0
-        # for_tile() re-packs a 3x3 filter with more than 64 output channels for a narrower tile on demand: only then is the fp32
-        # source kept (for filters built on the fly -- AttnBlock's folded 1x1s, 9.4 MB sub-pixel upsample filters, the per-step
-        # filters of training -- it would otherwise stay resident for the model's lifetime)
-        self._src = (w, bias, dgrad_pad) if (kh == 3 and not upsample_subpixel and not split and (cout if dgrad_pad is None else cin) > 64) else None
-        self._tiles = {}
-        lib = _lib.lib()
-        if cout_tile and not self.subpixel:
-            one = packed_conv_batch(w.unsqueeze(0), None if bias is None else bias.detach().float().reshape(1, -1), dgrad_pad, cout_tile)[0]
-            self.cout, self.cin, self.packed, self.bias, self.w16, self.cout_tile = one.cout, one.cin, one.packed, one.bias, None, cout_tile
-            return
-        if self.subpixel:
-            assert kh == 3 and dgrad_pad is None
-            self.cout, self.cin = cout, cin
-            n = lib.glare_conv2d_upsample_packed_weight_elems(cout, cin)
-            assert n > 0
-            self.packed = torch.empty(n, dtype=act_dtype(), device=w.device)
-            if feedback:
-                # the four phase filters (the taps of the 3x3 filter that read one source pixel, summed) rounded with error feedback per
-                # (phase, output channel) -- the sub-pixel form of filter_feedback_round: rows a = 0: r = 0 <- {0}, r = 1 <- {1, 2};
-                # a = 1: r = 0 <- {0, 1}, r = 1 <- {2}; columns alike
-                rows = {0: ((0,), (1, 2)), 1: ((0, 1), (2,))}
-                ph = torch.stack([torch.stack([torch.stack([w[:, :, list(rows[a][r])][:, :, :, list(rows[b][c])].sum(dim=(2, 3)) for c in (0, 1)], -1)
-                                               for r in (0, 1)], -2) for a in (0, 1) for b in (0, 1)])           # [4, cout, cin, 2, 2]
-                ph = filter_feedback_round(ph.reshape(4 * cout, cin, 2, 2))
-                check(lib.glare_conv2d_pack_weight_upsample_phases(ptr(ph), cout, cin, ptr(self.packed), stream_handle()),
-                      "glare_conv2d_pack_weight_upsample_phases")
-            else:
-                check(lib.glare_conv2d_pack_weight_upsample(ptr(w), cout, cin, ptr(self.packed), stream_handle()),
-                      "glare_conv2d_pack_weight_upsample")
-            self.bias = None if bias is None else bias.detach().float().contiguous()
-            return
-        self.cout, self.cin = (cout, cin) if dgrad_pad is None else (cin, dgrad_pad)
-        n = lib.glare_conv2d_packed_weight_elems(self.cout, self.cin, kh)
-        assert n > 0
-        self.packed = torch.empty(n, dtype=act_dtype(), device=w.device)
-        if dgrad_pad is None:
-            check(lib.glare_conv2d_pack_weight(ptr(w), cout, cin, kh, ptr(self.packed), stream_handle()),
-                  "glare_conv2d_pack_weight")
-        else:
-            check(lib.glare_conv2d_pack_weight_dgrad(ptr(w), cout, cin, kh, dgrad_pad, ptr(self.packed),
-                                                     stream_handle()), "glare_conv2d_pack_weight_dgrad")
-        self.bias = None if bias is None else bias.detach().float().contiguous()
-        self.w16 = None
-        self.w16_lo = None
+        assert w.shape[2] == w.shape[3] and w.shape[2] in (1, 3)
         if split:
-            self.cin = cin // split          # the conv's own input channels; the packed image holds `split` K segments of them
-            if kh == 1 and split == 3 and lib.glare_conv1x1_ws_split_supported(self.cin, cout):
-                # the fp32-class form on the weight-stationary kernel: the two halves of the filter as plain [Cout][Cin] images
-                # (segment 0 of `w` is the fp32 filter -- the pack kernel rounds it to w_hi --, segment 2 is w_lo)
-                w2 = w.reshape(cout, 3, self.cin)
-                self.w16, self.w16_lo = (torch.empty(cout, self.cin, dtype=act_dtype(), device=w.device) for _ in range(2))
-                for src, dst in ((w2[:, 0].contiguous(), self.w16), (w2[:, 2].contiguous(), self.w16_lo)):
-                    check(lib.glare_conv1x1_ws_pack_weight(ptr(src), cout, self.cin, ptr(dst), stream_handle()), "glare_conv1x1_ws_pack_weight")
-        if kh == 1 and dgrad_pad is None and not split and lib.glare_conv1x1_ws_supported(cin, cout):
-            # the weight-stationary 1x1 kernel (csrc/conv1x1.hip) takes the filter as plain bf16 [Cout][Cin]
-            self.w16 = torch.empty(cout, cin, dtype=act_dtype(), device=w.device)
-            check(lib.glare_conv1x1_ws_pack_weight(ptr(w), cout, cin, ptr(self.w16), stream_handle()), "glare_conv1x1_ws_pack_weight")
+            assert dgrad_pad is None and not upsample_subpixel and not cout_tile
+            fields = self._pack_split(w, bias, split)
+        elif upsample_subpixel:          # (ignores cout_tile: the sub-pixel kernel has one tile)
+            assert dgrad_pad is None
+            fields = self._pack_subpixel(w, bias, feedback)
+        elif cout_tile:
+            fields = self._pack_tiled(w, bias, dgrad_pad, cout_tile)
+        else:
+            fields = self._pack_plain(w, bias, dgrad_pad)
+        # AUTO_COUT_TILE re-packs a 3x3 filter with more than 64 output channels for a narrower tile on demand (conv2d): only then is
+        # the fp32 source kept (for filters built on the fly -- AttnBlock's folded 1x1s, 9.4 MB sub-pixel upsample filters, the per-step
+        # filters of training -- it would otherwise stay resident for the model's lifetime)
+        if w.shape[2] == 3 and not upsample_subpixel and not split and fields["cout"] > 64:
+            fields["src"] = (w, bias, dgrad_pad)
+        self._set(**fields)
+
+    def _set(self, ksize, cout, cin, packed, bias, split=0, k_wrap=0, subpixel=False, cout_tile=0, w16=None, w16_lo=None, src=None):
+        self.ksize, self.cout, self.cin, self.packed, self.bias = ksize, cout, cin, packed, bias
+        self.split, self.k_wrap, self.subpixel, self.cout_tile = int(split), k_wrap, bool(subpixel), cout_tile
+        self.w16, self.w16_lo, self._src, self._tiles, self._param = w16, w16_lo, src, {}, None
+
+    @staticmethod
+    def _pack_plain(w, bias, dgrad_pad, ws_image=True):
+        """The forward filter, or with dgrad_pad the filter of the data-gradient conv; a forward 1x1 filter the weight-stationary
+        kernel supports gets its plain image too."""
+        lib = _lib.lib()
+        cout, cin, kh, _ = w.shape
+        oc, ic = (cout, cin) if dgrad_pad is None else (cin, dgrad_pad)
+        n = lib.glare_conv2d_packed_weight_elems(oc, ic, kh)
+        assert n > 0
+        packed = torch.empty(n, dtype=act_dtype(), device=w.device)
+        if dgrad_pad is None:
+            check(lib.glare_conv2d_pack_weight(ptr(w), cout, cin, kh, ptr(packed), stream_handle()), "glare_conv2d_pack_weight")
+        else:
+            check(lib.glare_conv2d_pack_weight_dgrad(ptr(w), cout, cin, kh, dgrad_pad, ptr(packed), stream_handle()),
+                  "glare_conv2d_pack_weight_dgrad")
+        w16 = None
+        if ws_image and kh == 1 and dgrad_pad is None and lib.glare_conv1x1_ws_supported(cin, cout):
+            w16 = _ws_image(w, cout, cin)
+        return dict(ksize=kh, cout=oc, cin=ic, packed=packed, bias=_f32(bias), w16=w16)
+
+    @staticmethod
+    def _pack_tiled(w, bias, dgrad_pad, cout_tile):
+        """Packed for an explicit output-channel tile: the one-filter case of packed_conv_batch.  Like every batched pack it has NO
+        w16, also where the weight-stationary kernel supports the 1x1 filter -- not an oversight to mend in passing: the training
+        path's tiled PackCache entries launch (and are refreshed) this way, and a w16 would move them to another kernel."""
+        one = packed_conv_batch(w.unsqueeze(0), None if bias is None else bias.detach().float().reshape(1, -1), dgrad_pad, cout_tile)[0]
+        return dict(ksize=one.ksize, cout=one.cout, cin=one.cin, packed=one.packed, bias=one.bias, cout_tile=cout_tile)
+
+    @staticmethod
+    def _pack_subpixel(w, bias, feedback):
+        lib = _lib.lib()
+        cout, cin, kh, _ = w.shape
+        assert kh == 3
+        n = lib.glare_conv2d_upsample_packed_weight_elems(cout, cin)
+        assert n > 0
+        packed = torch.empty(n, dtype=act_dtype(), device=w.device)
+        if feedback:
+            # the four phase filters (the taps of the 3x3 filter that read one source pixel, summed) rounded with error feedback per
+            # (phase, output channel) -- the sub-pixel form of filter_feedback_round: rows a = 0: r = 0 <- {0}, r = 1 <- {1, 2};
+            # a = 1: r = 0 <- {0, 1}, r = 1 <- {2}; columns alike
+            rows = {0: ((0,), (1, 2)), 1: ((0, 1), (2,))}
+            ph = torch.stack([torch.stack([torch.stack([w[:, :, list(rows[a][r])][:, :, :, list(rows[b][c])].sum(dim=(2, 3)) for c in (0, 1)], -1)
+                                           for r in (0, 1)], -2) for a in (0, 1) for b in (0, 1)])           # [4, cout, cin, 2, 2]
+            ph = filter_feedback_round(ph.reshape(4 * cout, cin, 2, 2))
+            check(lib.glare_conv2d_pack_weight_upsample_phases(ptr(ph), cout, cin, ptr(packed), stream_handle()),
+                  "glare_conv2d_pack_weight_upsample_phases")
+        else:
+            check(lib.glare_conv2d_pack_weight_upsample(ptr(w), cout, cin, ptr(packed), stream_handle()), "glare_conv2d_pack_weight_upsample")
+        return dict(ksize=kh, cout=cout, cin=cin, packed=packed, bias=_f32(bias), subpixel=True)
+
+    @staticmethod
+    def _pack_split(w, bias, split):
+        """The fp32-class form: the K segments of split_filter() as one plain pack; a split-3 1x1 filter the weight-stationary kernel
+        supports also gets its two halves as plain images."""
+        cout, cin, kh, _ = w.shape
+        k_wrap = split_k_wrap(split, w)
+        segs = split_filter(w, split, reuse_kc=16 if k_wrap == 2 else 0)
+        fields = PackedConv._pack_plain(segs, bias, None, ws_image=False)
+        fields.update(cin=cin, split=split, k_wrap=k_wrap)
+        if kh == 1 and split == 3 and _lib.lib().glare_conv1x1_ws_split_supported(cin, cout):
+            halves = segs.reshape(cout, 3, cin)          # [w | w | w_lo]: the pack kernel rounds segment 0 to w_hi
+            fields["w16"], fields["w16_lo"] = _ws_image(halves[:, 0].contiguous(), cout, cin), _ws_image(halves[:, 2].contiguous(), cout, cin)
+        return fields
 
 
 def packed_conv_batch(weights, biases=None, dgrad_pad=None, cout_tile=0, split=0):
     """weights fp32 [n, cout, cin, k, k] (n filters of one shape) -> n PackedConv whose packed images come from ONE launch.
-    biases: fp32 [n, cout] or None; dgrad_pad, cout_tile, split as in PackedConv."""
+    biases: fp32 [n, cout] or None; dgrad_pad, cout_tile, split as in PackedConv.  A batched pack never has w16 / w16_lo or _src."""
     require_cuda(weights, biases)
     w = weights.detach().float().contiguous()
+    k_wrap = split_k_wrap(split, w)
     if split:
         assert dgrad_pad is None
-        k_wrap = 2 if (split == 3 and SPLIT_A_REUSE and w.shape[-1] == 3 and w.shape[2] % 16 == 0) else 1
         w = split_filter(w, split, reuse_kc=16 if k_wrap == 2 else 0)
-    else:
-        k_wrap = 0
     n, cout, cin, kh, kw = w.shape
     assert kh == kw and kh in (1, 3)
     lib = _lib.lib()
@@ -201,24 +234,13 @@ def packed_conv_batch(weights, biases=None, dgrad_pad=None, cout_tile=0, split=0
     packed = torch.empty(n, elems, dtype=act_dtype(), device=w.device)
     check(lib.glare_conv2d_pack_weight_batched(ptr(w), n, cout, cin, kh, 0 if dgrad_pad is None else dgrad_pad, cout_tile, ptr(packed),
                                                stream_handle()), "glare_conv2d_pack_weight_batched")
-    b = None if biases is None else biases.detach().float().contiguous()
-    out = []
-    for k in range(n):
-        pc = PackedConv.__new__(PackedConv)
-        pc.ksize, pc.subpixel, pc.cout, pc.cin, pc.packed, pc.w16, pc.cout_tile = kh, False, oc, ic // (split or 1), packed[k], None, cout_tile
-        pc.split, pc.k_wrap = int(split), k_wrap
-        pc.bias = None if b is None else b[k]
-        out.append(pc)
-    return out
+    b = _f32(biases)
+    return [PackedConv(_fields=dict(ksize=kh, cout=oc, cin=ic // (split or 1), packed=packed[k], bias=None if b is None else b[k],
+                                    split=split, k_wrap=k_wrap, cout_tile=cout_tile)) for k in range(n)]
 
 
-PACK_BLOCK_ELEMS = 2048   # GLARE_PACK_BLOCK_ELEMS (include/glare_hip.h)
-
-
-class _PackJob(ctypes.Structure):   # glare_pack_job (include/glare_hip.h)
-    _fields_ = [("w", ctypes.c_void_p), ("out", ctypes.c_void_p), ("total", ctypes.c_longlong), ("block_begin", ctypes.c_longlong),
-                ("cout", ctypes.c_int), ("cin", ctypes.c_int), ("ksize", ctypes.c_int), ("tn", ctypes.c_int), ("ksteps", ctypes.c_int),
-                ("n_stages", ctypes.c_int), ("cin_real", ctypes.c_int), ("kind", ctypes.c_int)]
+PACK_BLOCK_ELEMS = _K["GLARE_PACK_BLOCK_ELEMS"]
+_PackJob = _lib.structs()["glare_pack_job"]
 
 
 class PackCache:
@@ -256,7 +278,7 @@ class PackCache:
             if self.table is not None:
                 self._retired.append(self.table)   # a captured hipGraph may still launch the multi-shape pack from the old job
             self.table = None                      # table: it stays allocated (and correct for ITS entries) for the cache's lifetime
-        pc.bias = None if bias is None else bias.detach().float().contiguous()
+        pc.bias = _f32(bias)          # at EVERY call: one cached filter serves callers with different biases
         return pc
 
     def refresh(self):
@@ -267,7 +289,8 @@ class PackCache:
             jobs, begin = [], 0
             for (_, dgrad_pad, cout_tile), pc in self.entries.items():
                 cout, cin, kh, _ = pc._param.shape
-                kinds = [(1, pc.packed)] if dgrad_pad is not None else [(0, pc.packed)] + ([(2, pc.w16)] if pc.w16 is not None else [])
+                kinds = ([(_K["GLARE_PACK_DGRAD"], pc.packed)] if dgrad_pad is not None else
+                         [(_K["GLARE_PACK_FORWARD"], pc.packed)] + ([(_K["GLARE_PACK_PLAIN_BF16"], pc.w16)] if pc.w16 is not None else []))
                 for kind, dst in kinds:
                     j = _PackJob()
                     check(lib.glare_conv2d_pack_job_init(ctypes.byref(j), kind, ptr(pc._param), cout, cin, kh, dgrad_pad or 0, cout_tile,
@@ -334,15 +357,6 @@ def count_flops(family, flops):
         FLOP_COUNTER[family] = FLOP_COUNTER.get(family, 0.0) + float(flops)
 
 
-def _for_tile(pc, tile):
-    """The same filter packed for a narrower output-channel tile (cached on the PackedConv)."""
-    other = pc._tiles.get(tile)
-    if other is None:
-        w, bias, dgrad_pad = pc._src
-        other = pc._tiles[tile] = PackedConv(w, bias, dgrad_pad=dgrad_pad, cout_tile=tile)
-    return other
-
-
 # 3x3 convs of the cached (inference) filters pick the output-channel tile per launch (conv_cout_tile): a no-op at the BASELINE batch
 # (every launch fills the chip with the 128-wide tile), +20..60 % on the convs of small launches.  OFF by default: with a narrower
 # tile the fused GroupNorm statistics are summed in another fp32 order, and inference promises that a batch of 8 equals eight
@@ -363,74 +377,63 @@ class auto_cout_tile:
 CONV1X1_WEIGHT_STATIONARY = True   # False: every 1x1 conv through the implicit-GEMM kernel (conv_igemm.hip, KS = 1)
 
 
-def _conv1x1_ws(x, pc, cin, in_off, act, residual, res_off, out, out_off, gn_stats, hilo=False):
+class _GnStats:
+    """The fused GroupNorm statistics of a launch's output, for the kernel family `family` (glare_conv1x1_ws, glare_conv2d or
+    glare_conv2d_upsample): `partial`, which the launch's epilogue fills, is sized by <family>_gn_partial_elems(*dims); reduce(out), after
+    the launch, leaves stats[B, 1, 32, 2] of <family>_gn_reduce on the output as `out._gn_stats` (what groupnorm() consumes)."""
+
+    def __init__(self, family, dims, device):
+        self.lib, self.family, self.dims = _lib.lib(), family, dims
+        self.partial = torch.empty(getattr(self.lib, family + "_gn_partial_elems")(*dims), dtype=torch.float32, device=device)
+
+    def reduce(self, out):
+        stats = torch.empty(self.dims[0], 1, 32, 2, dtype=torch.float32, device=out.device)
+        check(getattr(self.lib, self.family + "_gn_reduce")(ptr(self.partial), ptr(stats), *self.dims, stream_handle()), self.family + "_gn_reduce")
+        out._gn_stats = stats  # a plain Python attribute, not a tensor property
+
+
+def _conv1x1_ws(x, pc, cin, in_off, act, residual, res_off, out, out_off, gn_stats, hilo):
+    """A 1x1 conv on the weight-stationary kernel (csrc/conv1x1.hip), through the entry point its operands need: a split-3 filter
+    contracts x and the filter as hi / lo pairs (glare_conv1x1_ws_split_bf16; the output a pair with hilo, else its 16-bit rounding),
+    a single-pass filter writes a pair (glare_conv1x1_ws_hilo_bf16) or a plain tensor (glare_conv1x1_ws_bf16)."""
+    xlo = getattr(x, "_lo", None) if pc.split else None
+    if pc.split:
+        assert xlo is not None and xlo.shape == x.shape and xlo.dtype == x.dtype and xlo.is_contiguous(), "a split-3 filter contracts the activation's hi / lo pair"
     B, H, W, pitch = x.shape
     N = H * W
     if out is None:
         out = torch.empty(B, H, W, pc.cout, dtype=act_dtype(), device=x.device)
     lib = _lib.lib()
-    gn_part = None
+    gn = None
     if gn_stats:
-        assert out_off == 0 and out.shape[3] == pc.cout
-        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(B, N, pc.cout), dtype=torch.float32, device=x.device)
-    if hilo:
-        out_lo = torch.empty_like(out)
-        rlo = getattr(residual, "_lo", None) if residual is not None else None
-        check(lib.glare_conv1x1_ws_hilo_bf16(ptr(x), pitch, in_off, ptr(pc.w16), 0, ptr(pc.bias), 0, ptr(residual), ptr(rlo),
-                                             residual.shape[3] if residual is not None else 0, res_off, ptr(out), ptr(out_lo), out.shape[3],
-                                             out_off, B, N, cin, pc.cout, ACT[act], ptr(gn_part),
-                                             stream_handle()), "glare_conv1x1_ws_hilo_bf16")
-        out._lo = out_lo
-    else:
-        _conv1x1_ws_plain(lib, x, pitch, in_off, pc, residual, res_off, out, out_off, B, N, cin, act, gn_part)
-    if gn_stats:
-        stats = torch.empty(B, 1, 32, 2, dtype=torch.float32, device=x.device)
-        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), B, N, pc.cout, stream_handle()),
-              "glare_conv1x1_ws_gn_reduce")
-        out._gn_stats = stats
-    return out
-
-
-def _conv1x1_ws_split(x, pc, cin, in_off, act, residual, res_off, out, out_off, gn_stats, hilo):
-    """The fp32-class 1x1 conv (PackedConv(split=3)) on the weight-stationary kernel (glare_conv1x1_ws_split_bf16): x and the filter as
-    hi / lo pairs, the output a pair (hilo) or its 16-bit rounding."""
-    xlo = getattr(x, "_lo", None)
-    assert xlo is not None and xlo.shape == x.shape and xlo.dtype == x.dtype and xlo.is_contiguous(), "a split-3 filter contracts the activation's hi / lo pair"
-    B, H, W, pitch = x.shape
-    N = H * W
-    if out is None:
-        out = torch.empty(B, H, W, pc.cout, dtype=act_dtype(), device=x.device)
-    lib = _lib.lib()
-    gn_part = None
-    if gn_stats:
-        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(B, N, pc.cout), dtype=torch.float32, device=x.device)
+        assert pc.split or (out_off == 0 and out.shape[3] == pc.cout)      # (the split form's callers are held to this by _ws_eligible)
+        gn = _GnStats("glare_conv1x1_ws", (B, N, pc.cout), x.device)
     out_lo = rlo = None
     if hilo:
-        out_lo = getattr(out, "_lo", None)
+        out_lo = getattr(out, "_lo", None)          # a caller-provided pair (out=...) keeps its lo half
         if out_lo is None:
             out_lo = torch.empty_like(out)
+    res_pitch = 0
     if residual is not None:
         assert residual.dtype == act_dtype() and residual.is_contiguous()
-        rlo = getattr(residual, "_lo", None)
-    check(lib.glare_conv1x1_ws_split_bf16(ptr(x), ptr(xlo), pitch, in_off, ptr(pc.w16), ptr(pc.w16_lo), ptr(pc.bias), ptr(residual),
-                                          ptr(rlo), residual.shape[3] if residual is not None else 0, res_off, ptr(out), ptr(out_lo),
-                                          out.shape[3], out_off, B, N, cin, pc.cout, ACT[act], ptr(gn_part),
-                                          stream_handle()), "glare_conv1x1_ws_split_bf16")
-    if gn_stats:
-        stats = torch.empty(B, 1, 32, 2, dtype=torch.float32, device=x.device)
-        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), B, N, pc.cout, stream_handle()),
-              "glare_conv1x1_ws_gn_reduce")
-        out._gn_stats = stats
+        rlo, res_pitch = getattr(residual, "_lo", None), residual.shape[3]
+    if pc.split:
+        check(lib.glare_conv1x1_ws_split_bf16(ptr(x), ptr(xlo), pitch, in_off, ptr(pc.w16), ptr(pc.w16_lo), ptr(pc.bias), ptr(residual),
+                                              ptr(rlo), res_pitch, res_off, ptr(out), ptr(out_lo), out.shape[3], out_off, B, N, cin, pc.cout,
+                                              ACT[act], ptr(gn and gn.partial), stream_handle()), "glare_conv1x1_ws_split_bf16")
+    elif hilo:
+        check(lib.glare_conv1x1_ws_hilo_bf16(ptr(x), pitch, in_off, ptr(pc.w16), 0, ptr(pc.bias), 0, ptr(residual), ptr(rlo), res_pitch,
+                                             res_off, ptr(out), ptr(out_lo), out.shape[3], out_off, B, N, cin, pc.cout, ACT[act], ptr(gn and gn.partial),
+                                             stream_handle()), "glare_conv1x1_ws_hilo_bf16")
+    else:
+        check(lib.glare_conv1x1_ws_bf16(ptr(x), pitch, in_off, ptr(pc.w16), ptr(pc.bias), ptr(residual), res_pitch, res_off, ptr(out),
+                                        out.shape[3], out_off, B, N, cin, pc.cout, ACT[act], ptr(gn and gn.partial), stream_handle()),
+              "glare_conv1x1_ws_bf16")
+    if gn is not None:
+        gn.reduce(out)
     if out_lo is not None:
         out._lo = out_lo
     return out
-
-
-def _conv1x1_ws_plain(lib, x, pitch, in_off, pc, residual, res_off, out, out_off, B, N, cin, act, gn_part):
-    check(lib.glare_conv1x1_ws_bf16(ptr(x), pitch, in_off, ptr(pc.w16), ptr(pc.bias), ptr(residual),
-                                    residual.shape[3] if residual is not None else 0, res_off, ptr(out), out.shape[3], out_off, B, N, cin,
-                                    pc.cout, ACT[act], ptr(gn_part), stream_handle()),
-          "glare_conv1x1_ws_bf16")
 
 
 def conv1x1_per_image(x, w16, bias, residual=None, gn_stats=False, hilo=False):
@@ -446,9 +449,7 @@ def conv1x1_per_image(x, w16, bias, residual=None, gn_stats=False, hilo=False):
     count_flops("conv k1", 2.0 * B * N * cin * cout)
     out = torch.empty(B, H, W, cout, dtype=act_dtype(), device=x.device)
     lib = _lib.lib()
-    gn_part = None
-    if gn_stats:
-        gn_part = torch.empty(lib.glare_conv1x1_ws_gn_partial_elems(B, N, cout), dtype=torch.float32, device=x.device)
+    gn = _GnStats("glare_conv1x1_ws", (B, N, cout), x.device) if gn_stats else None
     if residual is not None:
         assert residual.dtype == act_dtype() and residual.is_contiguous() and residual.shape == out.shape
     if hilo:
@@ -456,17 +457,14 @@ def conv1x1_per_image(x, w16, bias, residual=None, gn_stats=False, hilo=False):
         rlo = getattr(residual, "_lo", None) if residual is not None else None
         check(lib.glare_conv1x1_ws_hilo_bf16(ptr(x), cin, 0, ptr(w16), cout * cin, ptr(bias), cout, ptr(residual), ptr(rlo),
                                              cout if residual is not None else 0, 0, ptr(out), ptr(out_lo), cout, 0, B, N, cin, cout, 0,
-                                             ptr(gn_part), stream_handle()), "glare_conv1x1_ws_hilo_bf16")
+                                             ptr(gn and gn.partial), stream_handle()), "glare_conv1x1_ws_hilo_bf16")
         out._lo = out_lo
     else:
         check(lib.glare_conv1x1_ws_image_bf16(ptr(x), cin, 0, ptr(w16), cout * cin, ptr(bias), cout, ptr(residual),
-                                              cout if residual is not None else 0, 0, ptr(out), cout, 0, B, N, cin, cout, 0, ptr(gn_part),
+                                              cout if residual is not None else 0, 0, ptr(out), cout, 0, B, N, cin, cout, 0, ptr(gn and gn.partial),
                                               stream_handle()), "glare_conv1x1_ws_image_bf16")
     if gn_stats:
-        stats = torch.empty(B, 1, 32, 2, dtype=torch.float32, device=x.device)
-        check(lib.glare_conv1x1_ws_gn_reduce(ptr(gn_part), ptr(stats), B, N, cout, stream_handle()),
-              "glare_conv1x1_ws_gn_reduce")
-        out._gn_stats = stats
+        gn.reduce(out)
     return out
 
 
@@ -490,6 +488,36 @@ def attn_fold_groupnorm(stats, HW, gamma, beta, eps, wq, bq, wo, bo):
     return wq_b, bq_b, wo_b, bo_b
 
 
+def _count_conv_flops(pc, opix):
+    """ALGORITHMIC FLOPs of a conv launch of `opix` output pixels: an fp32-class (split) conv counts once, as in the LAUNCH_EVENTS path
+    and the bench text; the extra MFMA passes it executes are recorded under their own family so that no MFU derived from "conv k*"
+    is inflated 3x."""
+    if FLOP_COUNTER is not None:
+        flops = 2.0 * opix * pc.ksize ** 2 * pc.cin * pc.cout
+        count_flops("conv k%d" % pc.ksize, flops)
+        if pc.split:
+            count_flops("conv k%d extra fp32-class passes (executed, not algorithmic)" % pc.ksize, flops * (pc.split - 1))
+
+
+def _conv_desc(x, pc, cin, in_off):
+    """A glare_conv_desc with what every implicit-GEMM launch fills alike: the source, for an fp32-class filter the K order (k_wrap) and
+    with split = 3 the activation's lo half as second source ([x_hi | x_lo | x_hi] against [w_hi | w_hi | w_lo]), filter, bias, tile."""
+    B, H, W, pitch = x.shape
+    d = ConvDesc()
+    d.in_, d.B, d.H, d.W = x.data_ptr(), B, H, W
+    d.Cin, d.in_pitch, d.in_off = cin, pitch, in_off
+    if pc.split:
+        d.k_wrap = pc.k_wrap
+        if pc.split == 3:
+            xlo = getattr(x, "_lo", None)
+            assert xlo is not None and xlo.shape == x.shape and xlo.dtype == x.dtype and xlo.is_contiguous(), \
+                "a split-3 filter contracts the activation's hi / lo pair: x._lo is missing"
+            d.in2, d.Cin2, d.in2_pitch, d.in2_off = xlo.data_ptr(), cin, pitch, in_off
+    d.weight_packed, d.cout_tile, d.Cout, d.ksize = pc.packed.data_ptr(), pc.cout_tile, pc.cout, pc.ksize
+    d.bias = pc.bias.data_ptr() if pc.bias is not None else None
+    return d
+
+
 def conv2d_grouped(x, pcs, *, cin, in_step, out, out_step, in_off=0, out_off=0, act="none", out_mode=OUT_NHWC_BF16, out_lo=None):
     """len(pcs) independent convs of ONE shape in a single launch (glare_conv_desc.groups): conv g reads channels
     [in_off + g * in_step, + cin) of x and writes channels [out_off + g * out_step, + cout) of `out`.  pcs: the PackedConvs that
@@ -503,34 +531,33 @@ def conv2d_grouped(x, pcs, *, cin, in_step, out, out_step, in_off=0, out_off=0, 
         "grouped conv: filters must come from one packed_conv_batch()"
     if p0.bias is not None:
         assert all(pc.bias.data_ptr() == p0.bias.data_ptr() + g * p0.cout * 4 for g, pc in enumerate(pcs))
-    B, H, W, pitch = x.shape
-    d = ConvDesc()
-    d.in_, d.B, d.H, d.W = x.data_ptr(), B, H, W
-    d.Cin, d.in_pitch, d.in_off = cin, pitch, in_off
-    d.out, d.Cout, d.out_pitch, d.out_off = out.data_ptr(), p0.cout, out.shape[3], out_off
-    d.weight_packed = p0.packed.data_ptr()
-    d.bias = p0.bias.data_ptr() if p0.bias is not None else None
-    d.cout_tile = getattr(p0, "cout_tile", 0)
-    d.ksize, d.stride, d.upsample, d.act, d.out_mode = p0.ksize, 1, 0, ACT[act], out_mode
+    d = _conv_desc(x, p0, cin, in_off)
+    d.out, d.out_pitch, d.out_off = out.data_ptr(), out.shape[3], out_off
+    d.stride, d.upsample, d.act, d.out_mode = 1, 0, ACT[act], out_mode
     d.groups, d.group_in_step, d.group_out_step = G, in_step, out_step
-    split = getattr(p0, "split", 0)
-    if split:                                  # fp32-class: the hi / lo operand pair against [w_hi | w_hi | w_lo] (k_wrap)
-        d.k_wrap = getattr(p0, "k_wrap", 1) or 1
-        if split == 3:
-            xlo = getattr(x, "_lo", None)
-            assert xlo is not None and xlo.shape == x.shape and xlo.dtype == x.dtype and xlo.is_contiguous(), "split-3 filter: x needs its lo half"
-            d.in2, d.Cin2, d.in2_pitch, d.in2_off = xlo.data_ptr(), cin, pitch, in_off
     if out_lo is not None:
         assert out_mode == OUT_NHWC_BF16 and out_lo.shape == out.shape and out_lo.dtype == out.dtype and out_lo.is_contiguous()
         d.out_lo = out_lo.data_ptr()
         out._lo = out_lo
-    # ALGORITHMIC FLOPs: an fp32-class (split) conv counts once, as in the LAUNCH_EVENTS path and the bench text; the two extra MFMA
-    # passes it executes are recorded under their own family so that no MFU derived from "conv k*" is inflated 3x
-    count_flops("conv k%d" % p0.ksize, 2.0 * G * B * H * W * p0.ksize ** 2 * p0.cin * p0.cout)
-    if split:
-        count_flops("conv k%d extra fp32-class passes (executed, not algorithmic)" % p0.ksize, 2.0 * G * B * H * W * p0.ksize ** 2 * p0.cin * p0.cout * (split - 1))
+    _count_conv_flops(p0, G * x.shape[0] * x.shape[1] * x.shape[2])
     check(_lib.lib().glare_conv2d_bf16(ctypes.byref(d), stream_handle()), "glare_conv2d_bf16")
     return out
+
+
+def _ws_eligible(pc, x, cin, in_off, x2, stride, upsample, out_mode, out, out_off, residual, res_off, gn_stats, hilo, gn_prologue):
+    """May this launch take the weight-stationary 1x1 kernel (_conv1x1_ws) instead of the implicit-GEMM one?"""
+    if not (CONV1X1_WEIGHT_STATIONARY and x2 is None and stride == 1 and not upsample and out_mode == OUT_NHWC_BF16 and cin == pc.cin
+            and x.shape[3] % 8 == 0 and in_off % 8 == 0       # 16-byte rows: of the input, of a given output, of the residual
+            and (out is None or (out.dtype == act_dtype() and out.shape[3] % 8 == 0 and out_off % 8 == 0))
+            and (residual is None or (residual.shape[3] % 8 == 0 and res_off % 8 == 0))):
+        return False
+    whole = out is None or (out_off == 0 and out.shape[3] == pc.cout)      # the launch writes every channel of its output tensor
+    if pc.split == 0:       # single pass: the plain image, and fused statistics only into an output of its own
+        return pc.w16 is not None and (not gn_stats or out is None)
+    if pc.split == 3:       # fp32-class: both halves, no GroupNorm prologue; a pair or fused statistics only of a whole tensor (128-channel slabs)
+        return (pc.ksize == 1 and pc.w16_lo is not None and gn_prologue is None and (not hilo or whole)
+                and (not gn_stats or (pc.cout % 128 == 0 and whole)))
+    return False
 
 
 def conv2d(x, pc, *, x2=None, cin=None, in_off=0, cin2=None, in2_off=0, stride=1, upsample=False, act="none",
@@ -545,52 +572,27 @@ def conv2d(x, pc, *, x2=None, cin=None, in_off=0, cin2=None, in2_off=0, stride=1
     assert pc.packed.dtype == x.dtype, "filter packed under another precision"
     B, H, W, pitch = x.shape
     cin = pitch - in_off if cin is None else cin
-    split = getattr(pc, "split", 0)
-    if FLOP_COUNTER is not None:
-        opix = B * H * W * (4 if upsample else 1) // (stride * stride)
-        count_flops("conv k%d" % pc.ksize, 2.0 * opix * pc.ksize ** 2 * pc.cin * pc.cout)      # algorithmic: counted once (see conv2d_grouped)
-        if split:
-            count_flops("conv k%d extra fp32-class passes (executed, not algorithmic)" % pc.ksize, 2.0 * opix * pc.ksize ** 2 * pc.cin * pc.cout * (split - 1))
+    split = pc.split
+    _count_conv_flops(pc, B * H * W * (4 if upsample else 1) // (stride * stride))
     if hilo and pc.ksize == 1 and not split:
-        assert x2 is None and stride == 1 and not upsample and out is None and cin == pc.cin and getattr(pc, "w16", None) is not None
-        return _conv1x1_ws(x, pc, cin, in_off, act, residual, res_off, None, 0, gn_stats, hilo=True)
-    if (CONV1X1_WEIGHT_STATIONARY and getattr(pc, "w16", None) is not None and not split and x2 is None and stride == 1 and not upsample
-            and out_mode == OUT_NHWC_BF16 and cin == pc.cin and pitch % 8 == 0 and in_off % 8 == 0
-            and (out is None or (out.dtype == act_dtype() and out.shape[3] % 8 == 0 and out_off % 8 == 0))
-            and (residual is None or (residual.shape[3] % 8 == 0 and res_off % 8 == 0)) and (not gn_stats or out is None)):
-        if residual is not None:
-            assert residual.dtype == act_dtype() and residual.is_contiguous()
-        return _conv1x1_ws(x, pc, cin, in_off, act, residual, res_off, out, out_off, gn_stats)
-    if (split == 3 and pc.ksize == 1 and CONV1X1_WEIGHT_STATIONARY and getattr(pc, "w16_lo", None) is not None and x2 is None and stride == 1
-            and not upsample and out_mode == OUT_NHWC_BF16 and cin == pc.cin and pitch % 8 == 0 and in_off % 8 == 0 and gn_prologue is None
-            and (out is None or (out.dtype == act_dtype() and out.shape[3] % 8 == 0 and out_off % 8 == 0 and (not hilo or (out_off == 0 and out.shape[3] == pc.cout))))
-            and (residual is None or (residual.shape[3] % 8 == 0 and res_off % 8 == 0)) and (not gn_stats or (pc.cout % 128 == 0 and (out is None or (out_off == 0 and out.shape[3] == pc.cout))))):
-        return _conv1x1_ws_split(x, pc, cin, in_off, act, residual, res_off, out, out_off, gn_stats, hilo)
-    d = ConvDesc()
-    d.in_, d.in2 = x.data_ptr(), (x2.data_ptr() if x2 is not None else None)
-    d.B, d.H, d.W = B, H, W
-    d.Cin, d.in_pitch, d.in_off = cin, pitch, in_off
-    if split:      # fp32-class: K segments [x_hi | x_lo | x_hi] against the filter packed as [w_hi | w_hi | w_lo] (k_wrap)
+        # a single-pass 1x1 with a pair output exists on the weight-stationary kernel only (whatever CONV1X1_WEIGHT_STATIONARY says)
+        assert x2 is None and stride == 1 and not upsample and out is None and cin == pc.cin and pc.w16 is not None
+        return _conv1x1_ws(x, pc, cin, in_off, act, residual, res_off, None, 0, gn_stats, True)
+    if _ws_eligible(pc, x, cin, in_off, x2, stride, upsample, out_mode, out, out_off, residual, res_off, gn_stats, hilo, gn_prologue):
+        return _conv1x1_ws(x, pc, cin, in_off, act, residual, res_off, out, out_off, gn_stats, hilo)
+    cin2_total = 0
+    if split:      # fp32-class: _conv_desc adds the K segments
         assert x2 is None and not upsample and cin == pc.cin, (cin, pc.cin)
-        d.k_wrap = getattr(pc, "k_wrap", 1) or 1
-        assert d.k_wrap != 2 or gn_prologue is None
-        if split == 3:
-            x2 = getattr(x, "_lo", None)
-            assert x2 is not None and x2.shape == x.shape, "a split-3 filter contracts the activation's hi / lo pair: x._lo is missing"
-            cin2, in2_off = cin, in_off
-    if x2 is not None:
+        assert pc.k_wrap != 2 or gn_prologue is None
+    elif x2 is not None:
         assert x2.dtype == act_dtype() and x2.is_contiguous() and x2.shape[:3] == x.shape[:3]
-        d.in2 = x2.data_ptr()
-        d.Cin2 = x2.shape[3] - in2_off if cin2 is None else cin2
-        d.in2_pitch, d.in2_off = x2.shape[3], in2_off
-    assert pc.cin == d.Cin + (0 if split else d.Cin2), (pc.cin, d.Cin, d.Cin2)
+        cin2_total = x2.shape[3] - in2_off if cin2 is None else cin2
+    assert pc.cin == cin + cin2_total, (pc.cin, cin, cin2_total)
     IH, IW = (2 * H, 2 * W) if upsample else (H, W)
     OH, OW = ((IH + 1 - 3) // 2 + 1, (IW + 1 - 3) // 2 + 1) if stride == 2 else (IH, IW)
     if out is None:
-        if out_mode == OUT_NHWC_BF16:
-            out = torch.empty(B, OH, OW, pc.cout, dtype=act_dtype(), device=x.device)
-        elif out_mode == OUT_NHWC_F32:
-            out = torch.empty(B, OH, OW, pc.cout, dtype=torch.float32, device=x.device)
+        if out_mode in (OUT_NHWC_BF16, OUT_NHWC_F32):
+            out = torch.empty(B, OH, OW, pc.cout, dtype=act_dtype() if out_mode == OUT_NHWC_BF16 else torch.float32, device=x.device)
         else:
             pp = plane_pitch or OH * OW
             dt = torch.float32 if out_mode == OUT_PLANAR_F32 else act_dtype()
@@ -599,24 +601,25 @@ def conv2d(x, pc, *, x2=None, cin=None, in_off=0, cin2=None, in2_off=0, stride=1
                 out[:, :, OH * OW:].zero_()                                 # two-tensor attention reads whole 32-key groups): the
                                                                             # full 900 MB fill of the DCN's offset planes cost 0.1 ms
     assert out.is_contiguous()
-    if out_mode in (OUT_NHWC_BF16, OUT_NHWC_F32):
-        d.out_pitch = out.shape[3]
-    else:
-        d.out_pitch = out.shape[1]
-        d.plane_pitch = out.shape[2]
-    d.out, d.Cout, d.out_off = out.data_ptr(), pc.cout, out_off
     # (the hi / lo epilogue and the GroupNorm prologue exist for the 128-wide tile only: those launches keep it -- a narrower tile came
     # back as GLARE_ERR_UNSUPPORTED from the single-pass hi / lo stream at the training crops)
-    if (AUTO_COUT_TILE and pc.ksize == 3 and pc.cout > 64 and getattr(pc, "cout_tile", 0) == 0 and not getattr(pc, "subpixel", False)
-            and getattr(pc, "_src", None) is not None and not hilo and gn_prologue is None):
+    if (AUTO_COUT_TILE and pc.ksize == 3 and pc.cout > 64 and pc.cout_tile == 0 and not pc.subpixel and pc._src is not None
+            and not hilo and gn_prologue is None):
         tile = conv_cout_tile(B, OH, OW, pc.cout)
         if tile == 32 and gn_stats:
             tile = 64          # the fused GroupNorm statistics need 4-row wave slabs (128- and 64-wide tiles)
-        if tile:
-            pc = _for_tile(pc, tile)
-    d.weight_packed = pc.packed.data_ptr()
-    d.cout_tile = getattr(pc, "cout_tile", 0)
-    d.bias = pc.bias.data_ptr() if pc.bias is not None else None
+        if tile:       # the same filter packed for the narrower tile, cached on the PackedConv
+            if tile not in pc._tiles:
+                pc._tiles[tile] = PackedConv(pc._src[0], pc._src[1], dgrad_pad=pc._src[2], cout_tile=tile)
+            pc = pc._tiles[tile]
+    d = _conv_desc(x, pc, cin, in_off)
+    if x2 is not None:
+        d.in2, d.Cin2, d.in2_pitch, d.in2_off = x2.data_ptr(), cin2_total, x2.shape[3], in2_off
+    if out_mode in (OUT_NHWC_BF16, OUT_NHWC_F32):
+        d.out_pitch = out.shape[3]
+    else:
+        d.out_pitch, d.plane_pitch = out.shape[1], out.shape[2]
+    d.out, d.out_off = out.data_ptr(), out_off
     if residual is not None:
         assert residual.dtype == act_dtype() and residual.is_contiguous()
         d.residual, d.res_pitch, d.res_off = residual.data_ptr(), residual.shape[3], res_off
@@ -636,19 +639,14 @@ def conv2d(x, pc, *, x2=None, cin=None, in_off=0, cin2=None, in2_off=0, stride=1
         assert coef.dtype == torch.float32 and coef.is_contiguous() and tuple(coef.shape) == (B, cin, 2)
         assert pc.ksize == 3 and stride == 1 and x2 is None and not upsample and not split and not hilo and in_off == 0
         d.gn_coef, d.gn_swish = coef.data_ptr(), int(bool(swish))
-    subpixel = getattr(pc, "subpixel", False)
-    assert not subpixel or upsample, "a sub-pixel packed filter only implements the upsample conv"
-    d.ksize, d.stride, d.upsample, d.act, d.out_mode = pc.ksize, stride, (2 if subpixel else int(bool(upsample))), ACT[act], out_mode
+    assert not pc.subpixel or upsample, "a sub-pixel packed filter only implements the upsample conv"
+    d.stride, d.upsample, d.act, d.out_mode = stride, (2 if pc.subpixel else int(bool(upsample))), ACT[act], out_mode
     lib = _lib.lib()
-    gn_part = None
+    gn = None
     if gn_stats:  # GroupNorm statistics of the output, gathered by the epilogue (saves the consumer's read pass)
         assert out_mode == OUT_NHWC_BF16 and pc.cout % 128 == 0 and out_off == 0 and out.shape[3] == pc.cout
-        if subpixel:
-            n = lib.glare_conv2d_upsample_gn_partial_elems(B, H, W, pc.cout)
-        else:
-            n = lib.glare_conv2d_gn_partial_elems(B, OH, OW, pc.cout)
-        gn_part = torch.empty(n, dtype=torch.float32, device=x.device)
-        d.gn_partial = gn_part.data_ptr()
+        gn = _GnStats("glare_conv2d_upsample", (B, H, W, pc.cout), x.device) if pc.subpixel else _GnStats("glare_conv2d", (B, OH, OW, pc.cout), x.device)
+        d.gn_partial = gn.partial.data_ptr()
     if LAUNCH_EVENTS is not None and pc.ksize == 3:
         opix = B * OH * OW
         esz = 2 if out_mode in (OUT_NHWC_BF16, OUT_PLANAR_BF16) else 4
@@ -660,15 +658,8 @@ def conv2d(x, pc, *, x2=None, cin=None, in_off=0, cin2=None, in2_off=0, stride=1
             check(lib.glare_conv2d_bf16(ctypes.byref(d), stream_handle()), "glare_conv2d_bf16")
     else:
         check(lib.glare_conv2d_bf16(ctypes.byref(d), stream_handle()), "glare_conv2d_bf16")
-    if gn_stats:
-        stats = torch.empty(B, 1, 32, 2, dtype=torch.float32, device=x.device)
-        if subpixel:
-            check(lib.glare_conv2d_upsample_gn_reduce(ptr(gn_part), ptr(stats), B, H, W, pc.cout, stream_handle()),
-                  "glare_conv2d_upsample_gn_reduce")
-        else:
-            check(lib.glare_conv2d_gn_reduce(ptr(gn_part), ptr(stats), B, OH, OW, pc.cout, stream_handle()),
-                  "glare_conv2d_gn_reduce")
-        out._gn_stats = stats  # consumed by groupnorm(); plain Python attribute, not a tensor property
+    if gn is not None:
+        gn.reduce(out)
     if out_lo is not None:
         out._lo = out_lo
     return out
@@ -1071,8 +1062,8 @@ class PackedDcn:
         self.bias = None if bias is None else bias.detach().float().contiguous()
 
 
-MDCN_GENERAL_KERNEL = 1   # glare_hip.h: pin the general-extent MFMA kernel for this call
-MDCN_SINGLE_PASS = 2      # glare_hip.h: one MFMA per product on 16-bit operands (PackedDcn(single=True))
+MDCN_GENERAL_KERNEL = _K["GLARE_MDCN_GENERAL_KERNEL"]   # glare_hip.h: pin the general-extent MFMA kernel for this call
+MDCN_SINGLE_PASS = _K["GLARE_MDCN_SINGLE_PASS"]      # glare_hip.h: one MFMA per product on 16-bit operands (PackedDcn(single=True))
 
 
 def mdcn_forward_nhwc(x, om, pd, x_off=0, C=None, mask_is_logit=True, padding=1, flags=0):

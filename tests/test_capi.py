@@ -190,3 +190,98 @@ def test_size_queries_return_their_full_width_without_caller_types():
     assert one > 0 and lib.glare_groupnorm_workspace_bytes(2 ** 30, 64) == 2 ** 30 * one > 2 ** 32
     # glare_hip.h: [wz hi | lo] 2 x 2 KB, [W2 hi | lo] 2 x 8 KB, [W4 hi | lo] 2 x 8 KB, fp32 b2 [2][2][16] and b4[4]
     assert lib.glare_flow_step_fused_image_bytes() == 2 * 2048 + 4 * 8192 + 4 * (2 * 2 * 16 + 4)
+
+
+_STRUCTS = ("glare_conv_desc", "glare_pack_job")
+
+
+def test_struct_layouts_match_the_c_compiler(tmp_path):
+    """ops.ConvDesc / ops._PackJob are parsed from the header; a host C compiler (the oracle Makefile's $CC, default gcc) says what the
+    header means: sizeof and every field's offset and size, in declaration order."""
+    import keyword
+
+    from glare_amd import ops
+
+    classes = _lib.structs()
+    assert ops.ConvDesc is classes["glare_conv_desc"] and ops._PackJob is classes["glare_pack_job"]
+    src = open(_lib.HEADER_PATH).read()
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "glare_hip.h"', "int main(void) {"]
+    c_names = {}
+    for s in _STRUCTS:
+        body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (s, s), re.sub(r"/\*.*?\*/", " ", src, flags=re.S), flags=re.S).group(1)
+        c_names[s] = [n for decl in body.split(";") if decl.strip() for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
+        lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (s, s))
+        lines += ['  printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (s, f, s, f, s, f) for f in c_names[s]]
+    lines += ["  return 0;", "}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run([os.environ.get("CC", "gcc"), "-I", os.path.dirname(_lib.HEADER_PATH), "-o", exe, str(tmp_path / "layout.c")], check=True)
+    said = dict(line.split(" ", 1) for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
+    for s in _STRUCTS:
+        cls = classes[s]
+        assert len(c_names[s]) > 10 - 2 * (s == "glare_pack_job")
+        assert [f[0] for f in cls._fields_] == [n + "_" if keyword.iskeyword(n) else n for n in c_names[s]]
+        assert ctypes.sizeof(cls) == int(said[s]), s
+        for (py, _), c in zip(cls._fields_, c_names[s]):
+            off, size = map(int, said["%s.%s" % (s, c)].split())
+            assert (getattr(cls, py).offset, getattr(cls, py).size) == (off, size), (s, c)
+    assert len(ops.ConvDesc._fields_) == 36 and ops.ConvDesc._fields_[0][0] == "in_"
+
+
+def test_struct_parse_maps_the_closed_type_table_and_refuses_unknown_types():
+    c = ctypes
+    got = _lib.parse_structs("""
+        #define GLARE_N 4
+        typedef struct glare_thing {
+          const void* in;      /* a Python keyword */
+          int B, H,
+              W;               // three declarators, two lines
+          /* a block comment; with a semicolon, { a brace } and
+             a second line between fields */
+          long long total;
+          const float * bias;
+          size_t bytes; float eps;
+        } glare_thing;
+        int glare_use(const glare_thing* t);
+        typedef struct glare_other { void* p; } glare_other;""")
+    assert list(got) == ["glare_thing", "glare_other"]
+    assert got["glare_thing"]._fields_ == [("in_", c.c_void_p), ("B", c.c_int), ("H", c.c_int), ("W", c.c_int), ("total", c.c_longlong),
+                                           ("bias", c.c_void_p), ("bytes", c.c_size_t), ("eps", c.c_float)]
+    assert issubclass(got["glare_other"], c.Structure) and got["glare_other"]._fields_ == [("p", c.c_void_p)]
+    for bad in ("double x;", "unsigned n;", "struct { int a; } inner;", "int a[4];", "int a, *b;", "int a : 3;"):
+        with pytest.raises(_lib.GlareError):
+            _lib.parse_structs("typedef struct glare_x { int ok; %s } glare_x;" % bad)
+
+
+def test_constants_come_from_the_header():
+    from glare_amd import harness, ops
+
+    k = _lib.parse_constants("""
+        #define GLARE_HIP_H
+        #define GLARE_A 3   /* comment */
+        #define GLARE_B (-4)
+        // #define GLARE_C 5
+        #define OTHER 7
+        enum { GLARE_X = 0, GLARE_Y = 12 };""")
+    assert k == {"GLARE_A": 3, "GLARE_B": -4, "GLARE_X": 0, "GLARE_Y": 12}
+    assert ops.ACT == {"none": 0, "relu": 1, "sigmoid": 2, "swish": 3} and ops.ACT["swish"] == 3
+    assert (ops.OUT_NHWC_BF16, ops.OUT_NHWC_F32, ops.OUT_PLANAR_F32, ops.OUT_PLANAR_BF16) == (0, 1, 2, 3)
+    assert ops.PACK_BLOCK_ELEMS == 2048
+    assert (_lib.ERR_INVALID, _lib.ERR_LAUNCH, _lib.ERR_WORKSPACE, _lib.ERR_UNSUPPORTED) == (-1, -2, -3, -4)
+    assert (ops.MDCN_GENERAL_KERNEL, ops.MDCN_SINGLE_PASS) == (1, 2)
+    assert (harness.PAD_REFLECT101, harness.PAD_SYMMETRIC) == (0, 1)
+    consts = _lib.constants()
+    assert (consts["GLARE_PACK_FORWARD"], consts["GLARE_PACK_DGRAD"], consts["GLARE_PACK_PLAIN_BF16"]) == (0, 1, 2)
+
+
+def test_ops_does_not_probe_packed_conv_attributes():
+    """Every PackedConv has every field (ops.PackedConv.__slots__): consumers read the attribute, so that a misspelt name is an
+    AttributeError and not a silent "feature off"."""
+    from glare_amd import ops
+
+    fields = {"split", "w16", "w16_lo", "k_wrap", "cout_tile", "subpixel", "_src"}
+    assert fields < set(ops.PackedConv.__slots__)
+    probes = [node.lineno for node in ast.walk(ast.parse(open(ops.__file__).read()))
+              if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "getattr" and len(node.args) >= 2
+              and isinstance(node.args[1], ast.Constant) and node.args[1].value in fields]
+    assert not probes, probes
