@@ -78,10 +78,14 @@ def load_adam_state_dict(opt, sd):
     opt.t = step
 
 
-def save_training_state(path, trainer, epoch, iter_step, schedulers=()):
-    torch.save({"epoch": epoch, "iter": iter_step, "schedulers": [s.state_dict() for s in schedulers],
-                "optimizers": [adam_state_dict(trainer.opt)],
-                "scaler": trainer.opt.scaler_state_dict() if hasattr(trainer.opt, "scaler_state_dict") else dict(GRAD_SCALER_STATE)}, path)
+def save_training_state(path, trainer, epoch, iter_step, schedulers=(), extra=None):
+    """extra: further top-level keys (glare_amd.fit keeps its RNG states and its place in the epoch there); the reference's
+    resume_training reads the five keys above by name and ignores any other."""
+    state = {"epoch": epoch, "iter": iter_step, "schedulers": [s.state_dict() for s in schedulers],
+             "optimizers": [adam_state_dict(trainer.opt)],
+             "scaler": trainer.opt.scaler_state_dict() if hasattr(trainer.opt, "scaler_state_dict") else dict(GRAD_SCALER_STATE)}
+    state.update(extra or {})
+    torch.save(state, path)
 
 
 def resume_training(path_or_state, trainer, schedulers=()):

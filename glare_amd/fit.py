@@ -1,0 +1,382 @@
+"""Training driver: the loop around `Stage2Trainer` / `Stage3Trainer` (code/train_stage2.py, code/train_stage3.py:138-300 over
+models/base_model.py:46-83 and models/lr_scheduler.py:8-34), fed by a device-resident dataset (glare_amd.data.DeviceLoLDataset).
+
+    python -m glare_amd.fit stage3 --root LOLdataset --out run --net-g stage2_G.pth --net-vq vqgan.pkl
+    python -m glare_amd.fit stage3 --root LOLdataset --out run --resume run/training_state/500.state
+
+What is mirrored: the option keys and their per-stage values, the seeding, the index order of the reference's DataLoader, the
+augmentation draws, the learning-rate schedule with its warm-up override, the checkpoint cadence and the two checkpoint files
+(glare_amd.checkpoint: interchangeable with the reference's).  What is not: its logging stack (one JSON line per print_freq
+instead) and its validation block (dead code at the shipped val_freq; validation here is glare_amd.infer over the test split).
+World size 1."""
+import argparse
+import copy
+import json
+import os
+import random
+import time
+from collections import Counter
+
+import numpy as np
+import torch
+
+from . import checkpoint
+
+# confs/train_stage2_LOL.yml / confs/train_stage3_LOL.yml, the keys this driver reads, restated
+_COMMON_TRAIN = {"manual_seed": 10, "weight_decay_G": 0, "beta1": 0.9, "beta2": 0.99, "lr_scheme": "MultiStepLR", "warmup_iter": 10,
+                 "lr_steps_rel": [0.5, 0.75, 0.9, 0.95], "lr_gamma": 0.5, "val_freq": 0}
+_COMMON_DATA = {"use_shuffle": True, "use_flip": True, "use_crop": True, "use_rot": False, "noise_prob": 0, "noise_level": 5, "log_low": True,
+                "gamma_aug": False}
+DEFAULTS = {
+    "stage2": {"name": "train_stage2_LOL", "model": "LLFlow", "train_gt_ratio": 0.2,
+               "datasets": {"train": dict(_COMMON_DATA, batch_size=4, GT_size=320), "val": {"log_low": True}},
+               "network_G": {"train_RRDB": False},
+               "train": dict(_COMMON_TRAIN, lr_G=5e-4, niter=80000),
+               "logger": {"print_freq": 10, "save_checkpoint_freq": 1000}},
+    "stage3": {"name": "train_stage3_LOL", "model": "VQLLFLOWD", "train_gt_ratio": 0.0,
+               "datasets": {"train": dict(_COMMON_DATA, batch_size=2, GT_size=256), "val": {"log_low": True}},
+               "network_G": {"train_RRDB": False},
+               "train": dict(_COMMON_TRAIN, lr_G=5e-5, niter=40000),
+               "logger": {"print_freq": 5, "save_checkpoint_freq": 500}},
+}
+STATE_KEY = "glare_fit"      # the extra key of a `.state` file: RNG states and the place in the epoch (the reference ignores it)
+STEADY_FROM = 20             # the closing summary's ms per step leaves out this many steps
+
+
+def default_options(stage):
+    return copy.deepcopy(DEFAULTS[stage])
+
+
+def merge_options(opt, override):
+    """Nested dict update: `override` wins key by key (an --opt file names only what it changes)."""
+    for k, v in override.items():
+        if isinstance(v, dict) and isinstance(opt.get(k), dict):
+            merge_options(opt[k], v)
+        else:
+            opt[k] = v
+    return opt
+
+
+def load_options_file(path):
+    if path.endswith((".yml", ".yaml")):
+        try:
+            import yaml
+        except ImportError:
+            raise RuntimeError("%s: PyYAML is not installed; pass the options as a .json file" % path)
+        with open(path) as f:
+            return yaml.safe_load(f)
+    with open(path) as f:
+        return json.load(f)
+
+
+def set_random_seed(seed):
+    """utils/util.py set_random_seed."""
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(seed)
+
+
+class MultiStepSchedule:
+    """`MultiStepLR_Restart` at the shipped settings (restarts [0], weights [1], no inverse steps) = torch's MultiStepLR in its
+    chainable form, plus BaseModel.update_learning_rate's warm-up override, over the groups of a FlatAdam.  `lrs` is what
+    `optimizer.param_groups[i]['lr']` holds in the reference; it reaches the kernels as ONE device scalar (FlatAdam.set_lr_scale:
+    every group's lr moves by the same factor).  state_dict() carries torch's field names, so a `.state` file round-trips.
+
+    As in the reference, the override writes the group's lr and the scheduler then keeps multiplying THAT value: after the warm-up the
+    lr stays at initial_lr * (warmup_iter - 1) / warmup_iter until the first milestone."""
+
+    def __init__(self, opt, milestones, gamma, warmup_iter=-1):
+        self.opt = opt
+        self.milestones = Counter(int(m) for m in milestones)
+        self.gamma = gamma
+        self.warmup_iter = warmup_iter
+        self.base_lrs = [g.lr for g in opt.groups]
+        self.lrs = list(self.base_lrs)
+        self.last_epoch = 0            # torch's constructor performs the initial step
+        self._step_count = 1
+        self._last_lr = list(self.lrs)
+        self._scale = None
+
+    def update(self, cur_iter):
+        """update_learning_rate(cur_iter, warmup_iter): one scheduler step, then the warm-up override; returns group 0's lr."""
+        self.last_epoch += 1
+        self._step_count += 1
+        if self.last_epoch in self.milestones:
+            self.lrs = [lr * self.gamma ** self.milestones[self.last_epoch] for lr in self.lrs]
+        self._last_lr = list(self.lrs)
+        if cur_iter < self.warmup_iter:
+            self.lrs = [v / self.warmup_iter * cur_iter for v in self.base_lrs]
+        self.apply()
+        return self.lrs[0]
+
+    def apply(self):
+        scale = self.lrs[0] / self.base_lrs[0] if self.base_lrs[0] else 0.0
+        if scale != self._scale:             # a device write only when the factor moves: the warm-up steps and the milestones
+            self.opt.set_lr_scale(scale)
+            self._scale = scale
+
+    def state_dict(self):
+        return {"milestones": Counter(self.milestones), "gamma": self.gamma, "base_lrs": list(self.base_lrs), "last_epoch": self.last_epoch,
+                "_step_count": self._step_count, "_get_lr_called_within_step": False, "_last_lr": list(self._last_lr)}
+
+    def load_state_dict(self, sd):
+        self.milestones, self.gamma = Counter(sd["milestones"]), sd["gamma"]
+        self.base_lrs, self.last_epoch, self._step_count = list(sd["base_lrs"]), sd["last_epoch"], sd["_step_count"]
+        self._last_lr = list(sd.get("_last_lr", self.base_lrs))
+
+    # a `.state` file holds each group's CURRENT lr in its optimizer entry (torch's param_groups[i]['lr']); FlatGroup.lr is the base
+    def _swap_in_current(self):
+        for g, lr in zip(self.opt.groups, self.lrs):
+            g.lr = lr
+
+    def _swap_in_base(self):
+        for g, lr in zip(self.opt.groups, self.base_lrs):
+            g.lr = lr
+
+    def adopt_loaded(self):
+        """After checkpoint.resume_training: the groups' lr just loaded is the current one."""
+        self.lrs = [g.lr for g in self.opt.groups]
+        self._swap_in_base()
+        self._scale = None
+        self.apply()
+
+
+def make_schedule(opt, options):
+    tr = options["train"]
+    assert tr.get("lr_scheme", "MultiStepLR") == "MultiStepLR", "only MultiStepLR is built"
+    niter = int(tr["niter"])
+    return MultiStepSchedule(opt, [int(x * niter) for x in tr["lr_steps_rel"]], tr["lr_gamma"], tr.get("warmup_iter", -1))
+
+
+def epoch_batches(n, batch_size):
+    """The index batches of one epoch, in the order `DataLoader(dataset, batch_size, shuffle=True, drop_last=True)` yields them
+    for the same state of torch's default generator: its iterator draws a base seed first, then the RandomSampler seeds its own
+    generator -- two draws per epoch."""
+    torch.empty((), dtype=torch.int64).random_()
+    sampler = torch.utils.data.BatchSampler(torch.utils.data.RandomSampler(range(n)), batch_size, drop_last=True)
+    return [list(map(int, b)) for b in sampler]
+
+
+def _rng_state():
+    py = random.getstate()
+    kind, keys, pos, has_gauss, cached = np.random.get_state()
+    return {"python": [py[0], list(py[1]), py[2]], "numpy": [kind, torch.from_numpy(keys.astype(np.int64)), int(pos), int(has_gauss), float(cached)],
+            "torch": torch.get_rng_state()}
+
+
+def _set_rng_state(st):
+    py = st["python"]
+    random.setstate((py[0], tuple(py[1]), py[2]))
+    kind, keys, pos, has_gauss, cached = st["numpy"]
+    np.random.set_state((kind, keys.numpy().astype(np.uint32), pos, has_gauss, cached))
+    torch.set_rng_state(st["torch"])
+
+
+def _sync():
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+
+
+def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=None, validate_fn=None, log=None):
+    """The loop.  trainer: `.opt` (FlatAdam) and `.netG`; dataset: `len()` and `.batch(indices)`.  step_fn(gt, lq) -> loss (device
+    tensor, default trainer.step_tensor) and batch_fn(indices) -> (gt, lq) (default dataset.batch) are injectable, as is
+    validate_fn(iter) -> dict.  Returns the list of records it logged (one per print_freq, plus the closing summary)."""
+    step_fn = step_fn or trainer.step_tensor
+    batch_fn = batch_fn or dataset.batch
+    log = log or (lambda rec: print(json.dumps(rec), flush=True))
+    tr, lg = options["train"], options["logger"]
+    niter, batch_size = int(tr["niter"]), int(options["datasets"]["train"]["batch_size"])
+    print_freq, save_freq, val_freq = int(lg["print_freq"]), int(lg["save_checkpoint_freq"]), int(tr.get("val_freq") or 0)
+    n = len(dataset)
+    assert n >= batch_size, "%d training pairs cannot fill a batch of %d (drop_last)" % (n, batch_size)
+    os.makedirs(os.path.join(out_dir, "models"), exist_ok=True)
+    os.makedirs(os.path.join(out_dir, "training_state"), exist_ok=True)
+    trainer.opt.betas = (tr["beta1"], tr["beta2"])          # FlatAdam's own default is torch's 0.999
+    sched = make_schedule(trainer.opt, options)
+    set_random_seed(tr["manual_seed"])
+    epoch, step, order, done = 0, 0, None, 0
+    if resume:
+        st = torch.load(resume, map_location="cpu", weights_only=False) if isinstance(resume, str) else resume
+        epoch, step = checkpoint.resume_training(st, trainer, [sched])
+        sched.adopt_loaded()
+        if STATE_KEY in st:                  # written by this driver: continue the exact index / augmentation sequence
+            _set_rng_state(st[STATE_KEY]["rng"])
+            order, done = st[STATE_KEY]["epoch_order"], st[STATE_KEY]["batches_done"]
+
+    def save(epoch, step, order, done):
+        checkpoint.save_network(trainer.netG, os.path.join(out_dir, "models", "%d_G.pth" % step))
+        sched._swap_in_current()
+        try:
+            checkpoint.save_training_state(os.path.join(out_dir, "training_state", "%d.state" % step), trainer, epoch, step, [sched],
+                                           extra={STATE_KEY: {"rng": _rng_state(), "epoch_order": order, "batches_done": done}})
+        finally:
+            sched._swap_in_base()
+
+    records, first = [], step
+    t_win, n_win, t_batch, t_steady, last_loss, saved_at = time.perf_counter(), 0, 0.0, None, None, None
+    while step < niter:
+        if order is None:
+            order, done = epoch_batches(n, batch_size), 0
+        while done < len(order) and step < niter:
+            indices = order[done]
+            done += 1
+            step += 1
+            lr = sched.update(step)
+            t0 = time.perf_counter()
+            gt, lq = batch_fn(indices)
+            t_batch += time.perf_counter() - t0
+            last_loss = step_fn(gt, lq)
+            n_win += 1
+            rec = None
+            if step % print_freq == 0 or step == niter:
+                loss = float(last_loss)                     # the window's one device -> host read
+                now = time.perf_counter()
+                rec = {"epoch": epoch, "iter": step, "lr": lr, "loss": loss, "ms_per_step": 1e3 * (now - t_win) / n_win,
+                       "ms_batch": 1e3 * t_batch / n_win}
+            if step - first == STEADY_FROM:
+                _sync()
+                t_steady = time.perf_counter()
+            if validate_fn is not None and ((val_freq and step % val_freq == 0) or step == niter):
+                rec = rec or {"epoch": epoch, "iter": step, "lr": lr}
+                rec["val"] = validate_fn(step)
+            if step % save_freq == 0 or step == niter:
+                save(epoch, step, order, done)
+                saved_at = step
+            if rec is not None:
+                records.append(rec)
+                log(rec)
+                t_win, n_win, t_batch = time.perf_counter(), 0, 0.0       # validation and checkpoint time stay out of the next window
+        if done >= len(order):
+            order, epoch = None, epoch + 1
+    _sync()
+    summary = {"done": True, "iter": step, "epochs": epoch, "last_checkpoint": saved_at}
+    if t_steady is not None and step - first > STEADY_FROM:
+        summary["ms_per_step_after_%d" % STEADY_FROM] = 1e3 * (time.perf_counter() - t_steady) / (step - first - STEADY_FROM)
+    records.append(summary)
+    log(summary)
+    return records
+
+
+# ---- the command ---------------------------------------------------------------------------------------------------------------
+def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16"):
+    """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer."""
+    from . import modules as M
+    from .synthetic import seeded_init_
+    from .train import Stage2Trainer, Stage3Trainer
+
+    tr = options["train"]
+    net_hq = seeded_init_(M.VQModel().eval(), 1)
+    if stage == "stage2":
+        netG = seeded_init_(M.LLFlowVQGAN2(opt=options).train(), 2)
+    else:
+        netG = seeded_init_(M.VQLLFLOWDeformable().train(), 0)
+    if net_g:
+        checkpoint.load_network(net_g, netG, strict=False)           # VQLLFLOWD_model.py:53-63 loads with strict=False
+    if net_vq:
+        checkpoint.load_network(net_vq, net_hq, strict=False)
+    netG, net_hq = netG.to(device), net_hq.to(device)
+    if stage == "stage2":
+        return Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
+                             train_rrdb=bool(options["network_G"].get("train_RRDB", False)), device_state=graph, precision=precision)
+    return Stage3Trainer(netG, net_hq, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0), device_state=graph, precision=precision)
+
+
+def graphed_fns(trainer, dataset):
+    """(step_fn, batch_fn) that replay the step from a hipGraph: the GraphedStep is built on the first batch (after any resume, as
+    its capture_all() asks), and from then on batch() writes straight into its static inputs."""
+    from .train import GraphedStep
+
+    box = []
+
+    def batch_fn(indices):
+        return dataset.batch(indices, out_gt=box[0].gt, out_lq=box[0].lr) if box else dataset.batch(indices)
+
+    def step_fn(gt, lq):
+        if not box:
+            box.append(GraphedStep(trainer, gt, lq))
+        g = box[0]
+        return g.step_tensor(g.gt, g.lr)
+
+    return step_fn, batch_fn
+
+
+def make_validate(trainer, test_ds, precision, batch=8):
+    """PSNR / SSIM of the test split through the inference path (glare_amd.infer.run), images grouped by size."""
+    from . import infer
+
+    groups = {}
+    for low, high, _ in test_ds.pairs:
+        groups.setdefault(low.shape, []).append((low, high))
+
+    def validate(step):
+        was_training = trainer.netG.training
+        trainer.netG.eval()
+        rows = []
+        try:
+            for pairs in groups.values():
+                lows, gts = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+                rows.append(np.asarray(infer.run(len(pairs), batch=batch, pairs=(lows, gts), nets=(trainer.netG, trainer.net_hq), with_ssim=True,
+                                                 precision=precision)).reshape(len(pairs), 2))
+        finally:
+            trainer.netG.train(was_training)
+        rows = np.concatenate(rows)
+        return {"images": int(len(rows)), "psnr": float(rows[:, 0].mean()), "ssim": float(rows[:, 1].mean())}
+
+    return validate
+
+
+def main(argv=None):
+    from . import data as D
+
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("stage", choices=("stage2", "stage3"))
+    ap.add_argument("--root", required=True, help="dataset folder (v1: <root>/our485|eval15/{low,high}; v2: see --layout)")
+    ap.add_argument("--out", required=True, help="run folder: <out>/models/<iter>_G.pth, <out>/training_state/<iter>.state")
+    ap.add_argument("--layout", choices=sorted(D.LAYOUTS), default="v1")
+    ap.add_argument("--opt", default=None, help="options file (.json; .yml where PyYAML is installed) overriding the stage's defaults")
+    ap.add_argument("--niter", type=int, default=None)
+    ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--save-freq", type=int, default=None)
+    ap.add_argument("--val-freq", type=int, default=None, help="validate every N steps (default 0: only after the last step)")
+    ap.add_argument("--resume", default=None, help="a .state file; the weights come from models/<iter>_G.pth next to it unless --net-g is given")
+    ap.add_argument("--net-g", default=None, help="net_G checkpoint (reference format)")
+    ap.add_argument("--net-vq", default=None, help="VQGAN checkpoint (reference format)")
+    ap.add_argument("--graph", action="store_true", help="replay the step from a hipGraph (GraphedStep)")
+    ap.add_argument("--precision", choices=("fp16", "bf16"), default="fp16")
+    ap.add_argument("--no-val", action="store_true", help="skip the closing validation")
+    args = ap.parse_args(argv)
+
+    options = default_options(args.stage)
+    if args.opt:
+        merge_options(options, load_options_file(args.opt))
+    for value, (section, key) in ((args.niter, ("train", "niter")), (args.val_freq, ("train", "val_freq")),
+                                  (args.save_freq, ("logger", "save_checkpoint_freq"))):
+        if value is not None:
+            options[section][key] = value
+    if args.batch is not None:
+        options["datasets"]["train"]["batch_size"] = args.batch
+    assert torch.cuda.is_available(), "glare_amd.fit needs an MI355X: the HIP kernels are the only implementation"
+    device = torch.device("cuda", 0)
+    net_g = args.net_g
+    resume = None
+    if args.resume:
+        resume = torch.load(args.resume, map_location="cpu", weights_only=False)
+        if net_g is None:
+            net_g = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(args.resume))), "models", "%d_G.pth" % resume["iter"])
+    train_opt = dict(options["datasets"]["train"], root=args.root)
+    host_ds = D.LAYOUTS[args.layout](train_opt, train=True, all_opt=options)
+    dataset = D.DeviceLoLDataset(host_ds, device)
+    trainer = build_trainer(args.stage, options, device, net_g, args.net_vq, args.graph, args.precision)
+    step_fn, batch_fn = graphed_fns(trainer, dataset) if args.graph else (None, None)
+    validate_fn = None
+    if args.stage == "stage3" and not args.no_val:       # the inference path is the stage-3 network's; stage 2 has none to score
+        test_ds = D.LAYOUTS[args.layout](dict(options["datasets"].get("val", {}), root=args.root), train=False, all_opt=options)
+        if len(test_ds):
+            validate_fn = make_validate(trainer, test_ds, args.precision)
+    return fit(options, trainer, dataset, args.out, step_fn=step_fn, batch_fn=batch_fn, resume=resume, validate_fn=validate_fn)
+
+
+if __name__ == "__main__":
+    main()

@@ -35,18 +35,19 @@ def enhance_batch(netG, net_vq, imgs_u8, device, precision=None):
     return out
 
 
-def load_lol_pairs(root):
-    """uint8 (low, high) stacks of a LOL `eval15`-style folder (glare_amd.data.LoL_Dataset layout); all images one size."""
-    from .data import LoL_Dataset
+def load_lol_pairs(root, layout="v1"):
+    """uint8 (low, high) stacks of the test split of a LOL folder: layout "v1" = `<root>/eval15/{low,high}` (glare_amd.data.LoL_Dataset),
+    "v2" = `<root>/{Synthetic,Real_captured}/Test/{low,high}` (LoL_Dataset_v2); all images one size."""
+    from .data import LAYOUTS
 
-    ds = LoL_Dataset({"root": root}, train=False)
+    ds = LAYOUTS[layout]({"root": root}, train=False)
     lows = np.stack([p[0] for p in ds.pairs])
     gts = np.stack([p[1] for p in ds.pairs])
     return lows, gts
 
 
 def run(n_images, batch=8, h=400, w=600, seed=1234, root=None, net_g=None, net_vq=None, pairs=None, with_ssim=False, precision=None,
-        with_lpips=False, lpips_weights=None, nets=None):
+        with_lpips=False, lpips_weights=None, nets=None, layout="v1"):
     """Synthetic LOL-shaped pairs by default; `root` = a LOL dataset folder (eval15 split), `net_g` / `net_vq` = checkpoint
     files in the reference's format (glare_amd.checkpoint) -- without them the weights are name-seeded; `pairs` = (lows, gts)
     uint8 stacks [n,h,w,3] supplied by the caller.  with_ssim / with_lpips: the loop's other two metrics (infer_dataset_lol.py:152-153)
@@ -87,7 +88,7 @@ def run(n_images, batch=8, h=400, w=600, seed=1234, root=None, net_g=None, net_v
         lows, gts = pairs
         n_images, h, w = lows.shape[0], lows.shape[1], lows.shape[2]
     elif root:
-        lows, gts = load_lol_pairs(root)
+        lows, gts = load_lol_pairs(root, layout)
         n_images, h, w = lows.shape[0], lows.shape[1], lows.shape[2]
     else:
         lows = synthetic_lowlight(n_images, h, w, seed=seed)
@@ -164,6 +165,7 @@ def main():
     ap.add_argument("--height", type=int, default=400)
     ap.add_argument("--width", type=int, default=600)
     ap.add_argument("--root", default=None, help="LOL dataset folder (uses <root>/eval15/{low,high}/*.png)")
+    ap.add_argument("--layout", choices=("v1", "v2"), default="v1", help="v2: <root>/{Synthetic,Real_captured}/Test/{low,high}/*.png")
     ap.add_argument("--net-g", default=None, help="net_G checkpoint (reference format)")
     ap.add_argument("--net-vq", default=None, help="VQGAN checkpoint (reference format)")
     ap.add_argument("--ssim", action="store_true", help="also report SSIM (utils2.calculate_ssim) per image")
@@ -174,7 +176,7 @@ def main():
                          "result is not finite are re-run in bf16)")
     args = ap.parse_args()
     res = run(args.images, args.batch, args.height, args.width, root=args.root, net_g=args.net_g, net_vq=args.net_vq, with_ssim=args.ssim,
-              precision=args.precision, with_lpips=args.lpips, lpips_weights=args.lpips_weights)
+              precision=args.precision, with_lpips=args.lpips, lpips_weights=args.lpips_weights, layout=args.layout)
     if res is not None:
         world = int(os.environ.get("WORLD_SIZE", "1"))
         multi = args.ssim or args.lpips

@@ -755,6 +755,22 @@ int glare_harness_postprocess_u8(const float* out_nchw, int B, int Hp, int Wp, i
                                  unsigned char* out_hwc_u8, int* nonfinite_or_null, void* workspace, size_t workspace_bytes,
                                  glare_stream_t stream);
 
+/* ---- f2: one training batch from a device-resident uint8 dataset (LoL_Dataset.__getitem__, code/data/LoL_dataset.py:409-502) ----
+ * low_u8 / high_u8: every image of the dataset back to back, uint8 HWC, n_bytes each (a pair shares its offset and size).
+ * rows: int32 [B][GLARE_TRAIN_ROW_INTS], one row per sample = { byte offset low 32 bits, high 32 bits, H, W, y0, x0, crop_h, crop_w,
+ *   flip, k }.  Sample b of the batch is  rot90(flip(img[y0 : y0 + crop_h, x0 : x0 + crop_w]), k)  with flip = np.flip(axis = 1)
+ *   and rot90 = np.rot90(k, axes = (0, 1)), k in {0, 1, 3}; one thread per output pixel inverts rotation and flip, no intermediate.
+ * gt_nchw fp32 [B][3][out_h][out_w] = high / 255 (IEEE division); lq_nchw likewise = lq_lut_256[low]: a 256-entry device table, the
+ *   dataset's own log(clamp(v / 255 + 1e-3, min = 1e-3)) (or v / 255) evaluated once on the host, which makes LQ bit-identical to it.
+ * rows_host is the same table in host memory: it is validated here, before anything is launched (GLARE_ERR_INVALID for an image
+ *   outside the buffers, a crop outside its image, k not in {0, 1, 3}, a non-square crop with k != 0, a rotated crop that is not
+ *   out_h x out_w); rows_device is what the kernel reads -- a caller that replays a captured launch with new rows validates them
+ *   itself (the kernel skips any pixel whose source would lie outside its image or the buffers). */
+#define GLARE_TRAIN_ROW_INTS 10
+int glare_train_batch_u8(const unsigned char* low_u8, const unsigned char* high_u8, long long n_bytes, const int* rows_host,
+                         const int* rows_device, int B, int out_h, int out_w, const float* lq_lut_256, float* gt_nchw, float* lq_nchw,
+                         glare_stream_t stream);
+
 /* ---- f1: the rest of the stage-3 loss (VQLLFLOWD_model.py:209-223) -------------------------------------------------
  * glare_clamp01_f32 / _backward: sr = clamp(rec, 0, 1) with NaN -> 0 (:209-215) and torch.clamp's gradient mask.
  * MS-SSIM (modules/pytorch_msssim/__init__.py:21-98) on NHWC fp32 images: per pyramid level glare_ssim_forward_f32 writes the
