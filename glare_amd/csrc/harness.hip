@@ -203,6 +203,110 @@ __global__ void post_u8_count_kernel(const int* __restrict__ bad_partial, int B,
   nonfinite[b] = s;
 }
 
+// ---- the test scripts' "adjust" protocol (code/test_stage2.py:169-180, code/test_stage3.py:183-185, :203-204) ----------------
+constexpr int HBS = 128;  // blocks per image of the two kernels below (glare_harness_score_workspace_bytes: two 8-byte partials each)
+
+// level 1 of gain[b] = mean_gt / mean_out: per block, the fp64 sum of the window's RAW values (lr_out.reshape(B, -1).mean(1) is taken
+// before any clamp, :169 / :183) and the sum of 114 g0 + 587 g1 + 299 g2 over the uint8 ground truth -- the COLOR_BGR2GRAY weights on
+// RGB-ordered data (:170 / :184) in thousandths, which makes that half an exact integer.  One thread per pixel, grid-strided.
+__global__ __launch_bounds__(256) void gain_partial_kernel(const float* __restrict__ out, const uint8_t* __restrict__ gt, int Hp, int Wp,
+                                                           int top, int left, int h, int w, double* __restrict__ sum_out,
+                                                           unsigned long long* __restrict__ sum_gt) {
+  __shared__ double red[4];
+  __shared__ unsigned long long redg[4];
+  const int b = blockIdx.y;
+  const long long npix = (long long)h * w;
+  double sr = 0.0;
+  unsigned long long sg = 0;
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long long)HBS * 256) {
+    const int y = (int)(p / w), x = (int)(p - (long long)y * w);
+    const float* src = out + ((long long)b * 3 * Hp + top + y) * Wp + left + x;
+    const long long plane = (long long)Hp * Wp;
+    sr += ((double)src[0] + (double)src[plane]) + (double)src[2 * plane];
+    const uint8_t* g = gt + ((long long)b * npix + p) * 3;
+    sg += 114u * g[0] + 587u * g[1] + 299u * g[2];
+  }
+  for (int o = 32; o > 0; o >>= 1) { sr += __shfl_xor(sr, o, 64); sg += __shfl_xor(sg, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = sr; redg[threadIdx.x >> 6] = sg; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sum_out[(size_t)b * HBS + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    sum_gt[(size_t)b * HBS + blockIdx.x] = (redg[0] + redg[1]) + (redg[2] + redg[3]);
+  }
+}
+
+// level 2: the HBS partials of an image in index order -> gain[b] = (float)(mean_gt / mean_out)
+__global__ void gain_final_kernel(const double* __restrict__ sum_out, const unsigned long long* __restrict__ sum_gt, int B, long long npix,
+                                  float* __restrict__ gain) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double sr = 0.0;
+  unsigned long long sg = 0;
+  for (int k = 0; k < HBS; ++k) { sr += sum_out[(size_t)b * HBS + k]; sg += sum_gt[(size_t)b * HBS + k]; }
+  const double mean_out = sr / (3.0 * (double)npix);
+  const double mean_gt = (double)sg / (1000.0 * 255.0 * (double)npix);
+  gain[b] = (float)(mean_gt / mean_out);
+}
+
+// out_u8 = rgb(x * gain) = (uint8)(clamp(x * gain, 0, 1) * 255), truncating (rgb(), test_stage2.py:44-46; the clamp of :171 is the
+// one rgb() repeats), and the integer sum of (out_u8 - gt_u8)^2 per image: what Measure.psnr (skimage's peak_signal_noise_ratio on
+// two uint8 images) needs.  post_u8_kernel's layout: the output is one flat byte array, each thread owns one aligned 4-byte word of
+// it and reads the ground truth's word at the same offset; a word belongs to the image of its first byte, so the squared error of
+// the bytes it carries of the NEXT image goes to a second partial.  Integer partials: the sums are exact in any order.
+__global__ __launch_bounds__(256) void score_u8_kernel(const float* __restrict__ out, const float* __restrict__ gain,
+                                                       const uint8_t* __restrict__ gt, int B, int Hp, int Wp, int top, int left, int h, int w,
+                                                       uint8_t* __restrict__ dst, unsigned long long* __restrict__ sse_partial) {
+  __shared__ unsigned long long red[2][4];
+  const int b = blockIdx.y;
+  const long long n = 3LL * h * w, total = n * B;
+  const long long wlo = (n * b + 3) / 4, whi = (n * (b + 1) + 3) / 4;    // words whose first byte lies in image b
+  const float g_own = gain ? gain[b] : 1.f, g_next = gain && b + 1 < B ? gain[b + 1] : 1.f;
+  unsigned long long sse_own = 0, sse_next = 0;
+  for (long long wd = wlo + (long long)blockIdx.x * 256 + threadIdx.x; wd < whi; wd += (long long)HBS * 256) {
+    const long long k0 = wd * 4;
+    int bk = b;
+    long long r = k0 - n * b;
+    const long long p = r / 3;
+    int c = (int)(r - 3 * p);
+    int y = (int)(p / w), x = (int)(p - (long long)y * w);
+    const int nb = total - k0 < 4 ? (int)(total - k0) : 4;
+    uint32_t word = 0, gword = 0;
+    if (nb == 4) {
+      gword = *reinterpret_cast<const uint32_t*>(gt + k0);
+    } else {
+      for (int j = 0; j < nb; ++j) gword |= (uint32_t)gt[k0 + j] << (8 * j);
+    }
+    for (int j = 0; j < nb; ++j) {
+      const float v = out[(((long long)bk * 3 + c) * Hp + top + y) * Wp + left + x] * (bk == b ? g_own : g_next);
+      const uint32_t u = (uint8_t)(fminf(fmaxf(v, 0.f), 1.f) * 255.f);     // fmaxf(NaN, 0) = 0: a NaN (or 0 * inf) becomes 0
+      const int d = (int)u - (int)((gword >> (8 * j)) & 0xffu);
+      if (bk == b) sse_own += (unsigned)(d * d); else sse_next += (unsigned)(d * d);
+      word |= u << (8 * j);
+      if (++c == 3) { c = 0; if (++x == w) { x = 0; if (++y == h) { y = 0; ++bk; } } }
+    }
+    if (nb == 4) {
+      *reinterpret_cast<uint32_t*>(dst + k0) = word;
+    } else {
+      for (int j = 0; j < nb; ++j) dst[k0 + j] = (uint8_t)(word >> (8 * j));
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) { sse_own += __shfl_xor(sse_own, o, 64); sse_next += __shfl_xor(sse_next, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sse_own; red[1][threadIdx.x >> 6] = sse_next; }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    sse_partial[((size_t)threadIdx.x * B + b) * HBS + blockIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+__global__ void score_final_kernel(const unsigned long long* __restrict__ sse_partial, int B, long long* __restrict__ sse) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  unsigned long long s = 0;
+  for (int k = 0; k < HBS; ++k) s += sse_partial[(size_t)b * HBS + k];                                  // own words
+  if (b > 0)
+    for (int k = 0; k < HBS; ++k) s += sse_partial[((size_t)B + b - 1) * HBS + k];                      // the previous image's last word
+  sse[b] = (long long)s;
+}
+
 }  // namespace
 
 // restored float in [0,1] -> uint8 = rint(clip * 255): img_as_ubyte(restored), the image the reference's loop hands to imwrite
@@ -291,5 +395,42 @@ extern "C" int glare_harness_postprocess_u8(const float* out_nchw, int B, int Hp
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(post_u8_kernel, dim3(HBU, B), dim3(256), 0, s, out_nchw, B, Hp, Wp, top, left, h, w, out_hwc_u8, bad_partial);
   if (nonfinite_or_null) hipLaunchKernelGGL(post_u8_count_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, bad_partial, B, nonfinite_or_null);
+  return glare_launch_status();
+}
+
+// the window (top, left, h, w) of a [B][3][Hp][Wp] tensor as glare_harness_postprocess_u8 takes it: inside the tensor, grid.y = B,
+// one image's bytes below 2^31
+static bool score_window_ok(int B, int Hp, int Wp, int top, int left, int h, int w) {
+  if (B <= 0 || B > 65535 || h <= 0 || w <= 0 || top < 0 || left < 0) return false;
+  if ((long long)top + h > Hp || (long long)left + w > Wp) return false;
+  return 3LL * h * w <= 0x7fffffffLL;
+}
+
+extern "C" size_t glare_harness_score_workspace_bytes(int B) { return B <= 0 ? 0 : (size_t)B * HBS * 2 * sizeof(unsigned long long); }
+
+extern "C" int glare_harness_adjust_gain_f32(const float* out_nchw, const unsigned char* gt_hwc, int B, int Hp, int Wp, int top, int left,
+                                             int h, int w, float* gain, void* workspace, size_t workspace_bytes, glare_stream_t stream) {
+  if (!out_nchw || !gt_hwc || !gain || !score_window_ok(B, Hp, Wp, top, left, h, w)) return GLARE_ERR_INVALID;
+  if (!workspace || workspace_bytes < glare_harness_score_workspace_bytes(B)) return GLARE_ERR_WORKSPACE;
+  static_assert(sizeof(double) == sizeof(unsigned long long), "the two partial arrays share one element size");
+  double* sum_out = static_cast<double*>(workspace);
+  unsigned long long* sum_gt = reinterpret_cast<unsigned long long*>(sum_out + (size_t)B * HBS);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(gain_partial_kernel, dim3(HBS, B), dim3(256), 0, s, out_nchw, gt_hwc, Hp, Wp, top, left, h, w, sum_out, sum_gt);
+  hipLaunchKernelGGL(gain_final_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, sum_out, sum_gt, B, (long long)h * w, gain);
+  return glare_launch_status();
+}
+
+extern "C" int glare_harness_score_u8(const float* out_nchw, const float* gain_or_null, const unsigned char* gt_hwc, int B, int Hp, int Wp,
+                                      int top, int left, int h, int w, unsigned char* out_hwc_u8, long long* sse, void* workspace,
+                                      size_t workspace_bytes, glare_stream_t stream) {
+  if (!out_nchw || !gt_hwc || !out_hwc_u8 || !sse || !score_window_ok(B, Hp, Wp, top, left, h, w)) return GLARE_ERR_INVALID;
+  if (((uintptr_t)gt_hwc | (uintptr_t)out_hwc_u8) & 3) return GLARE_ERR_INVALID;      // both are read / written as 4-byte words
+  if (!workspace || workspace_bytes < glare_harness_score_workspace_bytes(B)) return GLARE_ERR_WORKSPACE;
+  unsigned long long* sse_partial = static_cast<unsigned long long*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(score_u8_kernel, dim3(HBS, B), dim3(256), 0, s, out_nchw, gain_or_null, gt_hwc, B, Hp, Wp, top, left, h, w, out_hwc_u8,
+                     sse_partial);
+  hipLaunchKernelGGL(score_final_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, sse_partial, B, sse);
   return glare_launch_status();
 }

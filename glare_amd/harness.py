@@ -80,6 +80,42 @@ def ssim_device(restored, gts_u8):
     return torch.cat(vals).double()
 
 
+# ---- the checkpoint sweep's "adjust" protocol (code/test_stage2.py:169-180, code/test_stage3.py:183-185, :203-204) --------------
+def _score_args(out_nchw, gts_u8, window):
+    _lib.require_cuda(out_nchw, gts_u8)
+    assert out_nchw.dtype == torch.float32 and out_nchw.dim() == 4 and out_nchw.shape[1] == 3 and out_nchw.is_contiguous()
+    B, _, Hp, Wp = out_nchw.shape
+    top, left, h, w = (0, 0, Hp, Wp) if window is None else window
+    assert gts_u8.dtype == torch.uint8 and tuple(gts_u8.shape) == (B, h, w, 3) and gts_u8.is_contiguous()
+    lib = _lib.main_lib()
+    nws = lib.glare_harness_score_workspace_bytes(B)
+    return lib, (B, Hp, Wp, top, left, h, w), torch.empty(max(nws, 1), dtype=torch.uint8, device=out_nchw.device), nws
+
+
+def adjust_gain_device(out_nchw, gts_u8, window=None):
+    """network output fp32 [B,3,Hp,Wp] and the uint8 ground truth [B,h,w,3] (device) -> fp32 [B] (device): mean_gt / mean_out of
+    the window (top, left, h, w) (default: the whole tensor), mean_out over the RAW values (same arithmetic as adjust_gain())."""
+    lib, (B, Hp, Wp, top, left, h, w), ws, nws = _score_args(out_nchw, gts_u8, window)
+    gain = torch.empty(B, dtype=torch.float32, device=out_nchw.device)
+    _lib.check(lib.glare_harness_adjust_gain_f32(_lib.ptr(out_nchw), _lib.ptr(gts_u8), B, Hp, Wp, top, left, h, w, _lib.ptr(gain), _lib.ptr(ws),
+                                                 nws, _lib.stream_handle()), "glare_harness_adjust_gain_f32")
+    return gain
+
+
+def score_device(out_nchw, gts_u8, gain=None, window=None):
+    """-> (uint8 [B,h,w,3] = rgb(out * gain) of the window, int64 [B] = sum (out_u8 - gt_u8)^2), both on the device; gain: fp32 [B]
+    (adjust_gain_device) or None = 1.  PSNR: psnr_u8(sse, 3 h w) on the host."""
+    lib, (B, Hp, Wp, top, left, h, w), ws, nws = _score_args(out_nchw, gts_u8, window)
+    if gain is not None:
+        _lib.require_cuda(gain)
+        assert gain.dtype == torch.float32 and tuple(gain.shape) == (B,) and gain.is_contiguous()
+    u8 = torch.empty(B, h, w, 3, dtype=torch.uint8, device=out_nchw.device)
+    sse = torch.empty(B, dtype=torch.int64, device=out_nchw.device)
+    _lib.check(lib.glare_harness_score_u8(_lib.ptr(out_nchw), _lib.ptr(gain), _lib.ptr(gts_u8), B, Hp, Wp, top, left, h, w, _lib.ptr(u8),
+                                          _lib.ptr(sse), _lib.ptr(ws), nws, _lib.stream_handle()), "glare_harness_score_u8")
+    return u8, sse
+
+
 # ---- unpaired enhancement (code/infer_unpaired.py:81-136): any size, no GT, uint8 out --------------------------------
 PAD_REFLECT101, PAD_SYMMETRIC = (_lib.constants()["GLARE_PAD_" + n] for n in ("REFLECT101", "SYMMETRIC"))     # include/glare_hip.h
 
@@ -140,6 +176,43 @@ def rgb_u8(x):
     x = np.asarray(x, dtype=np.float32)
     x = np.where(np.isnan(x), np.float32(0), x)
     return (np.clip(x, np.float32(0), np.float32(1)) * np.float32(255)).astype(np.uint8)
+
+
+def _window(out_nchw, window):
+    out_nchw = np.asarray(out_nchw, dtype=np.float32)
+    top, left, h, w = (0, 0) + out_nchw.shape[2:] if window is None else window
+    return out_nchw[:, :, top:top + h, left:left + w]
+
+
+def adjust_gain(out_nchw, gts_u8, window=None):
+    """Host restatement of the test scripts' gain (test_stage2.py:169-171, test_stage3.py:183-185) in fp64: float array
+    [B,3,Hp,Wp] and uint8 [B,h,w,3] -> fp32 [B] = mean_gt / mean_out.  mean_out is `lr_out.reshape(B, -1).mean(1)` of the window's
+    RAW values (nothing is clamped first); mean_gt the gray mean of the ground truth / 255 with gray_mean()'s weights."""
+    x = _window(out_nchw, window).astype(np.float64)
+    g = np.asarray(gts_u8).astype(np.float64)
+    mean_out = x.reshape(x.shape[0], -1).mean(axis=1)
+    mean_gt = (0.114 * g[..., 0] + 0.587 * g[..., 1] + 0.299 * g[..., 2]).reshape(g.shape[0], -1).mean(axis=1) / 255
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (mean_gt / mean_out).astype(np.float32)
+
+
+def score_u8(out_nchw, gts_u8, gain=None, window=None):
+    """Host restatement of glare_harness_score_u8: -> (uint8 [B,h,w,3] = rgb_u8(out * gain) of the window, int64 [B] = the sum of
+    squared differences to the uint8 ground truth).  The product is taken in fp32, as the device (and torch, on the fp32 output) does."""
+    x = _window(out_nchw, window)
+    if gain is not None:
+        with np.errstate(invalid="ignore", over="ignore"):
+            x = x * np.asarray(gain, dtype=np.float32).reshape(-1, 1, 1, 1)
+    u8 = np.ascontiguousarray(rgb_u8(x).transpose(0, 2, 3, 1))
+    d = u8.astype(np.int64) - np.asarray(gts_u8).astype(np.int64)
+    return u8, (d * d).reshape(d.shape[0], -1).sum(axis=1)
+
+
+def psnr_u8(sse, n):
+    """skimage.metrics.peak_signal_noise_ratio of two uint8 images (Measure.psnr, code/Measure.py:43-45) from their sum of squared
+    differences over n values: 10 log10(255^2 / (sse / n)) in fp64, inf at sse = 0 (as it returns)."""
+    sse = int(sse)
+    return math.inf if sse == 0 else 10 * math.log10(255.0 ** 2 / (sse / n))
 
 
 def preprocess(img_u8):

@@ -11,6 +11,7 @@ import random
 
 import torch
 
+from .. import ops
 from ._base import HipModule, to_nchw, to_nhwc
 from .ConditionEncoder import ConEncoder1
 from .FlowUpsamplerNet import FlowUpsamplerNet
@@ -57,6 +58,18 @@ class LLFlowVQGAN2(HipModule):
         pixels = gt_latent.shape[1] * gt_latent.shape[2]
         nll = -(logdet + logp) / (math.log(2.0) * pixels)
         return (z, nll, logdet) if want_z else nll
+
+    def enhance_nhwc(self, net_hq, lr, precision=None):
+        """The stage-2 image (code/test_stage2.py:157-161: get_sr, then net_hq.decode): conditional encoder -> reverse flow ->
+        codebook -> the VQGAN decoder's RGB head, every intermediate NHWC on the device.  lr: fp32 NCHW log-domain image batch,
+        sides multiples of 4.  precision: as VQLLFLOWDeformable.reverse_flow_nhwc.  -> that method's dict; "out" is the fp32 NCHW
+        image, "code_feats" the decoder's two feature maps.  Bit-identical to to_nchw(forward(reverse=True)) -> net_hq.decode
+        under the same precision (the codes pass through decode's straight-through sum)."""
+        with ops.use_precision(ops.inference_precision(precision)):
+            enc = self.RRDB.forward_nhwc(lr)
+            latent = self.flowUpsamplerNet.decode_nhwc(enc["color_map"], enc["cond_feat"])
+            idx, out, code_feats = net_hq.decode_nhwc(latent, want_image=True, straight_through=True)
+        return {"out": out, "latent": latent, "indices": idx, "enc": enc, "code_feats": code_feats}
 
     def forward(self, gt=None, lr=None, z=None, eps_std=None, reverse=False, epses=None, reverse_with_grad=False, lr_enc=None,
                 add_gt_noise=False, step=None, y_label=None, align_condition_feature=False, get_color_map=False):

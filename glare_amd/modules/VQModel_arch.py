@@ -34,10 +34,13 @@ class VQModel(HipModule):
     def encode(self, x):  # VQModel_arch.py:74-79
         return to_nchw(self.encode_nhwc(x)), None
 
-    def decode_nhwc(self, z, want_image=False):
-        """z: fp32 NHWC latent [B,h,w,3] -> (indices, image or None, [feat@half, feat@full])."""
+    def decode_nhwc(self, z, want_image=False, straight_through=False):
+        """z: fp32 NHWC latent [B,h,w,3] -> (indices, image or None, [feat@half, feat@full]).
+        straight_through: the codes as `decode` hands them on, z + (z_q - z) in fp32 (quantize.py:298 -- not always z_q to the bit)."""
         B, H, W, C = z.shape
         idx, zq = self.quantize.quantize_tokens(z.view(-1, C))
+        if straight_through:
+            zq = z.view(-1, C) + (zq - z.view(-1, C))
         quant2 = self._conv1x1_latent(self.post_quant_conv, zq.view(B, H, W, C))
         img, feats = self.decoder.forward_nhwc(quant2, want_image=want_image)
         return idx, img, feats

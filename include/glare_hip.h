@@ -755,6 +755,27 @@ int glare_harness_postprocess_u8(const float* out_nchw, int B, int Hp, int Wp, i
                                  unsigned char* out_hwc_u8, int* nonfinite_or_null, void* workspace, size_t workspace_bytes,
                                  glare_stream_t stream);
 
+/* ---- the checkpoint sweep's "adjust" protocol (code/test_stage2.py:169-180, code/test_stage3.py:183-185, :203-204) ------------
+ * Both read the [h][w] window at (top, left) of the network output fp32 NCHW [B][3][Hp][Wp], as glare_harness_postprocess_u8 takes
+ * it, and the uint8 ground truth HWC [B][h][w][3].  B <= 65535, 3 h w < 2^31; workspace >= glare_harness_score_workspace_bytes(B).
+ * glare_harness_adjust_gain_f32: gain[b] (fp32 [B]) = (float)(mean_gt / mean_out).  mean_out = the mean of all 3 h w RAW values of
+ *   the window -- lr_out.reshape(B, -1).mean(dim=1) is taken before any clamp (test_stage2.py:169, test_stage3.py:183); mean_gt =
+ *   mean(0.114 ch0 + 0.587 ch1 + 0.299 ch2) / 255 of the ground truth: cv2.COLOR_BGR2GRAY applied to RGB-ordered data
+ *   (test_stage2.py:170, test_stage3.py:184).  fp64 sums of the output in a fixed two-level order, exact integer sums of the ground
+ *   truth (the weights in thousandths): the same bits from run to run.
+ * glare_harness_score_u8: out_hwc_u8 [B][h][w][3] = (uint8)(fminf(fmaxf(x * gain[b], 0), 1) * 255.0f) in fp32 -- rgb(clamp(lr_out *
+ *   gain, 0, 1)) (test_stage2.py:44-46, :171; test_stage3.py:185), which TRUNCATES; a NaN becomes 0; gain_or_null NULL = 1, the
+ *   unadjusted rgb(lr_out) of test_stage2.py:165 / :179 -- the arithmetic of glare_harness_postprocess_u8.  sse[b] (int64 [B]) =
+ *   sum (out_u8 - gt_u8)^2, exact.  The caller's PSNR is 10 log10(255^2 / (sse / (3 h w))) in fp64: Measure.psnr
+ *   (code/Measure.py, skimage.metrics.peak_signal_noise_ratio on the two uint8 images; inf at sse = 0).  out_hwc_u8 and gt_hwc
+ *   are accessed as 4-byte words: both 4-byte aligned. */
+size_t glare_harness_score_workspace_bytes(int B);
+int glare_harness_adjust_gain_f32(const float* out_nchw, const unsigned char* gt_hwc, int B, int Hp, int Wp, int top, int left, int h,
+                                  int w, float* gain, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+int glare_harness_score_u8(const float* out_nchw, const float* gain_or_null, const unsigned char* gt_hwc, int B, int Hp, int Wp, int top,
+                           int left, int h, int w, unsigned char* out_hwc_u8, long long* sse, void* workspace, size_t workspace_bytes,
+                           glare_stream_t stream);
+
 /* ---- f2: one training batch from a device-resident uint8 dataset (LoL_Dataset.__getitem__, code/data/LoL_dataset.py:409-502) ----
  * low_u8 / high_u8: every image of the dataset back to back, uint8 HWC, n_bytes each (a pair shares its offset and size).
  * rows: int32 [B][GLARE_TRAIN_ROW_INTS], one row per sample = { byte offset low 32 bits, high 32 bits, H, W, y0, x0, crop_h, crop_w,
