@@ -730,6 +730,7 @@ def groupnorm(x, gamma, beta, swish=True, eps=1e-6, cin=None, in_off=0, pair=Fal
         return y
     nws = lib.glare_groupnorm_workspace_bytes(B, H * W)
     ws = _workspace(nws, x.device)
+    assert ws.dtype == torch.uint8    # ws.numel() below is the workspace size in BYTES
     y = torch.empty(B, H, W, C, dtype=act_dtype(), device=x.device)
     check(lib.glare_groupnorm_swish_bf16(ptr(x), pitch, in_off, ptr(gamma), ptr(beta), ptr(y), B, H * W, C, eps, int(swish), ptr(ws),
                                          ws.numel(), stream_handle()),

@@ -301,7 +301,7 @@ int glare_flow_tail_f32(float* z_nhwc3, const float* h4, const float* hF, int hF
                         long long n_pixels, const float* M_3x3_host, const float* t_3_host, float eps,
                         glare_stream_t stream);
 /* The whole coupling step as ONE launch (round 6; csrc/flow_fused.hip): the three launches above and the two convs between them
- * (FlowAffineCouplingsAblation.py:143-151: 3x3 65 -> 64, ReLU, 1x1 64 -> 64, ReLU, Conv2dZeros 3x3 64 -> 4) fused per 8 x 32
+ * (FlowAffineCouplingsAblation.py:143-151: 3x3 65 -> 64, ReLU, 1x1 64 -> 64, ReLU, Conv2dZeros 3x3 64 -> 4) fused per 16 x 40
  * pixel tile with the halo recomputed, every contraction in the fp32-class form (hi / lo operand pairs, three MFMA products),
  * h1 / h2 chained through registers.  z_in -> z_out, both fp32 [B*H*W][3], must be DIFFERENT buffers (a tile reads the
  * neighbouring tiles' z_in channel 0).  `image`: the step's filters as the kernel's fragment image, 16-B aligned,
