@@ -341,6 +341,26 @@ def l1_clamp_loss(rec, gt_nchw):
 
 
 @_lib.keeps_precision
+class L1LossFn(torch.autograd.Function):
+    """Plain mean |rec - gt| on the NHWC output (stage 1: no clamp, so that a reconstruction outside [0, 1] is still pulled back)."""
+
+    @staticmethod
+    def forward(ctx, rec, gt_nchw):
+        loss, grad = T.l1_loss(rec.contiguous(), gt_nchw.float().contiguous())
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None     # as L1ClampLossFn: an image-sized (3-channel) scale by the scalar upstream gradient
+
+
+def l1_loss(rec, gt_nchw):
+    return L1LossFn.apply(rec, gt_nchw)
+
+
+@_lib.keeps_precision
 class Clamp01Fn(torch.autograd.Function):
     """sr = rec.clamp(0, 1); sr[isnan] = 0 (VQLLFLOWD_model.py:209-215)."""
 
@@ -460,6 +480,57 @@ def nhwc_to_nchw(x):
 
 def to_nhwc_f32(x_nchw):
     return ops.nchw_to_nhwc(x_nchw, bf16=False)
+
+
+@_lib.keeps_precision
+class NchwToNhwcFn(torch.autograd.Function):
+    """fp32 NCHW -> fp32 NHWC, differentiable: the module surface of VectorQuantizer2.forward (quantize.py:276)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return ops.nchw_to_nhwc(x.float().contiguous(), bf16=False)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.nhwc_to_nchw(g.float().contiguous())
+
+
+def nchw_to_nhwc_f32(x):
+    return NchwToNhwcFn.apply(x)
+
+
+@_lib.keeps_precision
+class VQStraightThroughFn(torch.autograd.Function):
+    """The codebook layer with a tape (VectorQuantizer2.forward, quantize.py:276-298): nearest code (the inference kernel, bit-exact),
+    loss = (w_z + w_e) mean (z_q - z)^2 and the straight-through output z + (z_q - z).  Backward (csrc/vq_train.hip): the latent gets
+    the output's gradient plus the w_z term, the codebook the w_e term as a fixed-order per-code sum -- the straight-through path
+    sends it nothing.  All fp32; the loss's upstream gradient (the GradScaler's scale under fp16) stays on the device."""
+
+    @staticmethod
+    def forward(ctx, z, codebook, w_z, w_e):
+        flat = z.float().contiguous().view(-1, z.shape[-1])
+        cb = codebook.detach().float().contiguous()
+        idx, zq = ops.vq_nearest(flat, cb)
+        s, st = T.vq_loss_sum(flat, zq)
+        ctx.cfg = (float(w_z), float(w_e), cb.shape[0], tuple(z.shape), tuple(codebook.shape))
+        ctx.save_for_backward(flat, zq, idx)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        return st.view(z.shape), s[0] * ((float(w_z) + float(w_e)) / flat.numel()), idx
+
+    @staticmethod
+    def backward(ctx, g_st, g_loss, _g_idx):
+        w_z, w_e, n_codes, zshape, cshape = ctx.cfg
+        flat, zq, idx = ctx.saved_tensors
+        g = None if g_st is None else g_st.float().contiguous().view(flat.shape)
+        gl = torch.zeros(1, dtype=torch.float32, device=flat.device) if g_loss is None else g_loss.detach().float().reshape(1).contiguous()
+        dz, de = T.vq_backward(flat, zq, idx, g, gl, n_codes, w_z, w_e, want_dz=ctx.needs_input_grad[0], want_de=ctx.needs_input_grad[1])
+        return (None if dz is None else dz.view(zshape)), (None if de is None else de.view(cshape)), None, None
+
+
+def vq_straight_through(z_nhwc, codebook, w_z, w_e):
+    """z fp32 NHWC [.., 3], codebook fp32 [K, 3] -> (z + (z_q - z) like z, loss scalar, idx int64 [N])."""
+    return VQStraightThroughFn.apply(z_nhwc, codebook, w_z, w_e)
 
 
 @_lib.keeps_precision

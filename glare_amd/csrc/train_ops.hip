@@ -568,6 +568,26 @@ __global__ __launch_bounds__(256) void l1_loss_kernel(const float* __restrict__ 
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Stage-1 pixel loss: plain mean |rec - gt| (no clamp: a clamp would zero the gradient of a reconstruction outside [0, 1]);
+// grad = sign(rec - gt) / n, a NaN in rec propagates into both.  Layouts as l1_loss_kernel.
+__global__ __launch_bounds__(256) void l1_plain_loss_kernel(const float* __restrict__ rec, const float* __restrict__ gt, long long HW, int C,
+                                                            long long total, float inv_n, float* __restrict__ grad,
+                                                            float* __restrict__ partial) {
+  __shared__ float red[4];
+  float acc = 0.f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int c = (int)(i % C);
+    const long long pix = i / C, b = pix / HW, q = pix % HW;
+    const float d = rec[i] - gt[(b * C + c) * HW + q];
+    acc += fabsf(d);
+    grad[i] = d > 0.f ? inv_n : (d < 0.f ? -inv_n : (d == d ? 0.f : d));
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // out = a + b (+ c): the gradient accumulation at a fan-out point of the tape (an activation read by several consumers);
 // bf16 in / out, fp32 add.  Keeps the accumulation on this library instead of the autograd engine's own add.
 __global__ __launch_bounds__(256) void add_bf16_kernel(const a16_t* __restrict__ a, const a16_t* __restrict__ b,
@@ -869,6 +889,18 @@ extern "C" int glare_l1_clamp_loss_f32(const float* rec_nhwc, const float* gt_nc
   if (!workspace || workspace_bytes < (size_t)blocks * sizeof(float)) return GLARE_ERR_WORKSPACE;
   const float inv_n = 1.0f / (float)total;
   hipLaunchKernelGGL(l1_loss_kernel, dim3(blocks), dim3(256), 0, ST(stream), rec_nhwc, gt_nchw, HW, C, total, inv_n, grad_nhwc,
+                     static_cast<float*>(workspace));
+  return glare_reduce_parts_f32(static_cast<const float*>(workspace), blocks, 1, inv_n, loss_out, 0, stream);
+}
+
+extern "C" int glare_l1_loss_f32(const float* rec_nhwc, const float* gt_nchw, int B, long long HW, int C, float* loss_out,
+                                 float* grad_nhwc, void* workspace, size_t workspace_bytes, glare_stream_t stream) {
+  if (!rec_nhwc || !gt_nchw || !loss_out || !grad_nhwc || B <= 0 || HW <= 0 || C <= 0) return GLARE_ERR_INVALID;
+  const long long total = (long long)B * HW * C;
+  const int blocks = (int)(cdivll(total, 1024) < 1 ? 1 : (cdivll(total, 1024) > 512 ? 512 : cdivll(total, 1024)));
+  if (!workspace || workspace_bytes < (size_t)blocks * sizeof(float)) return GLARE_ERR_WORKSPACE;
+  const float inv_n = 1.0f / (float)total;
+  hipLaunchKernelGGL(l1_plain_loss_kernel, dim3(blocks), dim3(256), 0, ST(stream), rec_nhwc, gt_nchw, HW, C, total, inv_n, grad_nhwc,
                      static_cast<float*>(workspace));
   return glare_reduce_parts_f32(static_cast<const float*>(workspace), blocks, 1, inv_n, loss_out, 0, stream);
 }

@@ -1,8 +1,14 @@
-"""Training driver: the loop around `Stage2Trainer` / `Stage3Trainer` (code/train_stage2.py, code/train_stage3.py:138-300 over
-models/base_model.py:46-83 and models/lr_scheduler.py:8-34), fed by a device-resident dataset (glare_amd.data.DeviceLoLDataset).
+"""Training driver: the loop around `Stage1Trainer` / `Stage2Trainer` / `Stage3Trainer` (code/train_stage2.py,
+code/train_stage3.py:138-300 over models/base_model.py:46-83 and models/lr_scheduler.py:8-34), fed by a device-resident dataset
+(glare_amd.data.DeviceLoLDataset).
 
+    python -m glare_amd.fit stage1 --root LOLdataset --out prior [--net-vq start.pth]
     python -m glare_amd.fit stage3 --root LOLdataset --out run --net-g stage2_G.pth --net-vq vqgan.pkl
     python -m glare_amd.fit stage3 --root LOLdataset --out run --resume run/training_state/500.state
+
+Stage 1 trains the VQGAN prior itself (VQModel_arch.py:98-101, 148-157) on the ground-truth half of the pairs and writes
+<out>/models/<iter>_VQ.pth under the reference's VQModel key names: what `--net-vq` of stages 2 and 3, `evaluate` and `enhance` load.
+The reference ships no stage-1 configuration (its prior is a download): `lr_G` 1e-4 is a starting point, not a tuned value.
 
 What is mirrored: the option keys and their per-stage values, the seeding, the index order of the reference's DataLoader, the
 augmentation draws, the learning-rate schedule with its warm-up override, the checkpoint cadence and the two checkpoint files
@@ -28,6 +34,13 @@ _COMMON_TRAIN = {"manual_seed": 10, "weight_decay_G": 0, "beta1": 0.9, "beta2": 
 _COMMON_DATA = {"use_shuffle": True, "use_flip": True, "use_crop": True, "use_rot": False, "noise_prob": 0, "noise_level": 5, "log_low": True,
                 "gamma_aug": False}
 DEFAULTS = {
+    # no file of the reference: its stage-1 network and optimizer are VQModel_arch.py:98-101, 148-157 (Adam, betas (0.5, 0.9)); crop,
+    # batch, lr and schedule are this driver's starting point
+    "stage1": {"name": "train_stage1_LOL", "model": "VQModel", "train_gt_ratio": 0.0,
+               "datasets": {"train": dict(_COMMON_DATA, batch_size=4, GT_size=256), "val": {"log_low": True}},
+               "network_G": {"train_RRDB": False},
+               "train": dict(_COMMON_TRAIN, beta1=0.5, beta2=0.9, lr_G=1e-4, niter=80000, codebook_weight=1.0),
+               "logger": {"print_freq": 10, "save_checkpoint_freq": 1000}},
     "stage2": {"name": "train_stage2_LOL", "model": "LLFlow", "train_gt_ratio": 0.2,
                "datasets": {"train": dict(_COMMON_DATA, batch_size=4, GT_size=320), "val": {"log_low": True}},
                "network_G": {"train_RRDB": False},
@@ -205,8 +218,10 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
             _set_rng_state(st[STATE_KEY]["rng"])
             order, done = st[STATE_KEY]["epoch_order"], st[STATE_KEY]["batches_done"]
 
+    tag = getattr(trainer, "checkpoint_tag", "G")        # stage 1 writes <iter>_VQ.pth: the file `--net-vq` takes
+
     def save(epoch, step, order, done):
-        checkpoint.save_network(trainer.netG, os.path.join(out_dir, "models", "%d_G.pth" % step))
+        checkpoint.save_network(trainer.netG, os.path.join(out_dir, "models", "%d_%s.pth" % (step, tag)))
         sched._swap_in_current()
         try:
             checkpoint.save_training_state(os.path.join(out_dir, "training_state", "%d.state" % step), trainer, epoch, step, [sched],
@@ -264,9 +279,17 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
     """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer."""
     from . import modules as M
     from .synthetic import seeded_init_
-    from .train import Stage2Trainer, Stage3Trainer
+    from .train import Stage1Trainer, Stage2Trainer, Stage3Trainer
 
     tr = options["train"]
+    if stage == "stage1":
+        if graph:
+            raise ValueError(GRAPH_REFUSAL)
+        net = seeded_init_(M.VQModel().train(), 1)
+        if net_vq:
+            checkpoint.load_network(net_vq, net, strict=False)
+        return Stage1Trainer(net.to(device), lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0),
+                             codebook_weight=tr.get("codebook_weight", 1.0), precision=precision)
     net_hq = seeded_init_(M.VQModel().eval(), 1)
     if stage == "stage2":
         netG = seeded_init_(M.LLFlowVQGAN2(opt=options).train(), 2)
@@ -281,6 +304,9 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
         return Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
                              train_rrdb=bool(options["network_G"].get("train_RRDB", False)), device_state=graph, precision=precision)
     return Stage3Trainer(netG, net_hq, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0), device_state=graph, precision=precision)
+
+
+GRAPH_REFUSAL = "--graph is not available for stage1: its step is not captured into a hipGraph (GraphedStep covers stages 2 and 3)"
 
 
 def graphed_fns(trainer, dataset):
@@ -327,11 +353,40 @@ def make_validate(trainer, test_ds, precision, batch=8):
     return validate
 
 
-def main(argv=None):
+def make_validate_stage1(trainer, test_ds, precision):
+    """Mean PSNR of decode(encode(gt)) over the test split's ground-truth images, through the inference kernels (VQModel.encode_nhwc /
+    decode_nhwc as stages 2 and 3 call them); an image whose sides are no multiple of 4 (the encoder's stride) is padded at the
+    bottom / right by reflection and scored on its own window.  uint8 PSNR as glare_amd.evaluate (harness.score_device / psnr_u8)."""
+    from . import harness, ops
+
+    def validate(step):
+        net = trainer.netG
+        was_training = net.training
+        net.eval()
+        vals = []
+        try:
+            with torch.no_grad(), ops.use_precision(ops.inference_precision(precision)):
+                for _, high, _ in test_ds.pairs:
+                    h, w = high.shape[:2]
+                    padded = np.pad(high, [(0, -h % 4), (0, -w % 4), (0, 0)], "symmetric")
+                    x = torch.from_numpy(np.ascontiguousarray(padded.transpose(2, 0, 1)[None]).astype(np.float32) / 255).cuda()
+                    _, img, _ = net.decode_nhwc(net.encode_nhwc(x), want_image=True, straight_through=True)
+                    gt = torch.from_numpy(np.array(high[None])).cuda()                   # (a copy: the dataset's arrays are read-only)
+                    _, sse = harness.score_device(img.float().contiguous(), gt, window=(0, 0, h, w))
+                    vals.append(harness.psnr_u8(int(sse[0]), 3 * h * w))
+        finally:
+            net.train(was_training)
+        return {"images": len(vals), "psnr": float(np.mean(vals))}
+
+    return validate
+
+
+def parse_args(argv=None):
+    """The command line -> (args, options): the stage's defaults, the --opt file over them, the single-key switches over that."""
     from . import data as D
 
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("stage", choices=("stage2", "stage3"))
+    ap.add_argument("stage", choices=("stage1", "stage2", "stage3"))
     ap.add_argument("--root", required=True, help="dataset folder (v1: <root>/our485|eval15/{low,high}; v2: see --layout)")
     ap.add_argument("--out", required=True, help="run folder: <out>/models/<iter>_G.pth, <out>/training_state/<iter>.state")
     ap.add_argument("--layout", choices=sorted(D.LAYOUTS), default="v1")
@@ -340,13 +395,16 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--save-freq", type=int, default=None)
     ap.add_argument("--val-freq", type=int, default=None, help="validate every N steps (default 0: only after the last step)")
-    ap.add_argument("--resume", default=None, help="a .state file; the weights come from models/<iter>_G.pth next to it unless --net-g is given")
+    ap.add_argument("--resume", default=None, help="a .state file; the weights come from models/<iter>_G.pth (stage1: <iter>_VQ.pth) next to it "
+                                                   "unless --net-g (stage1: --net-vq) is given")
     ap.add_argument("--net-g", default=None, help="net_G checkpoint (reference format)")
-    ap.add_argument("--net-vq", default=None, help="VQGAN checkpoint (reference format)")
-    ap.add_argument("--graph", action="store_true", help="replay the step from a hipGraph (GraphedStep)")
+    ap.add_argument("--net-vq", default=None, help="VQGAN checkpoint (reference format); stage1: the weights to start from")
+    ap.add_argument("--graph", action="store_true", help="replay the step from a hipGraph (GraphedStep; stages 2 and 3)")
     ap.add_argument("--precision", choices=("fp16", "bf16"), default="fp16")
     ap.add_argument("--no-val", action="store_true", help="skip the closing validation")
     args = ap.parse_args(argv)
+    if args.graph and args.stage == "stage1":
+        ap.error(GRAPH_REFUSAL)
 
     options = default_options(args.stage)
     if args.opt:
@@ -357,24 +415,35 @@ def main(argv=None):
             options[section][key] = value
     if args.batch is not None:
         options["datasets"]["train"]["batch_size"] = args.batch
+    return args, options
+
+
+def main(argv=None):
+    from . import data as D
+
+    args, options = parse_args(argv)
     assert torch.cuda.is_available(), "glare_amd.fit needs an MI355X: the HIP kernels are the only implementation"
     device = torch.device("cuda", 0)
-    net_g = args.net_g
+    net_g, net_vq = args.net_g, args.net_vq
     resume = None
     if args.resume:
         resume = torch.load(args.resume, map_location="cpu", weights_only=False)
-        if net_g is None:
-            net_g = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(args.resume))), "models", "%d_G.pth" % resume["iter"])
+        models = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(args.resume))), "models")
+        if args.stage == "stage1":
+            net_vq = net_vq or os.path.join(models, "%d_VQ.pth" % resume["iter"])
+        elif net_g is None:
+            net_g = os.path.join(models, "%d_G.pth" % resume["iter"])
     train_opt = dict(options["datasets"]["train"], root=args.root)
     host_ds = D.LAYOUTS[args.layout](train_opt, train=True, all_opt=options)
     dataset = D.DeviceLoLDataset(host_ds, device)
-    trainer = build_trainer(args.stage, options, device, net_g, args.net_vq, args.graph, args.precision)
+    trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision)
     step_fn, batch_fn = graphed_fns(trainer, dataset) if args.graph else (None, None)
     validate_fn = None
-    if args.stage == "stage3" and not args.no_val:       # the inference path is the stage-3 network's; stage 2 has none to score
+    # stage 3 scores the inference path, stage 1 the prior's own reconstruction of the ground truth; stage 2 has nothing to score
+    if args.stage in ("stage1", "stage3") and not args.no_val:
         test_ds = D.LAYOUTS[args.layout](dict(options["datasets"].get("val", {}), root=args.root), train=False, all_opt=options)
         if len(test_ds):
-            validate_fn = make_validate(trainer, test_ds, args.precision)
+            validate_fn = (make_validate_stage1 if args.stage == "stage1" else make_validate)(trainer, test_ds, args.precision)
     return fit(options, trainer, dataset, args.out, step_fn=step_fn, batch_fn=batch_fn, resume=resume, validate_fn=validate_fn)
 
 

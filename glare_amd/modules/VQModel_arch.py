@@ -1,6 +1,9 @@
-"""Frozen VQGAN prior `net_hq` (mirrors code/models/modules/VQModel_arch.py:14-91, encode/decode)."""
+"""VQGAN prior `net_hq` (mirrors code/models/modules/VQModel_arch.py:14-101): encode / decode as the frozen prior of stages 2 and 3,
+and the taped autoencoder `forward(input) -> (dec, diff)` that stage 1 trains (:98-101)."""
+import torch
 import torch.nn as nn
 
+from .. import autograd as A
 from .. import ops
 from ._base import HipModule, to_nchw, to_nhwc
 from .encoder_decoder import Decoder, Encoder
@@ -52,3 +55,25 @@ class VQModel(HipModule):
         dec, feats = self.decoder.forward_nhwc(quant2, want_image=True)
         self.last_indices = info[2]
         return dec, emb_loss, [to_nchw(f) for f in feats]
+
+    def train_nhwc(self, x_nchw):
+        """The whole autoencoder with a tape (VQModel_arch.py:98-101, forward = decode(encode(x))): x fp32 NCHW image ->
+        (xrec fp32 NHWC, qloss scalar, idx int64 [B*h*w]).  The two 1x1 convs of the 3-channel latent run the thin-input conv with
+        weight, bias and data gradients; the codebook layer is autograd.vq_straight_through (csrc/vq_train.hip)."""
+        q = self.quantize
+        h, _ = self.encoder.train_nhwc(x_nchw)
+        z = A.conv2d_small(h, self.quant_conv.weight, self.quant_conv.bias, layout="nhwc", out_f32=True)
+        w_z, w_e = (1.0, q.beta) if q.legacy else (q.beta, 1.0)
+        zq, qloss, idx = A.vq_straight_through(z, q.embedding.weight, w_z, w_e)
+        quant2 = A.conv2d_small(zq, self.post_quant_conv.weight, self.post_quant_conv.bias, layout="nhwc", out_f32=True)
+        xrec, _ = self.decoder.train_nhwc(quant2)
+        self.last_indices = idx
+        return xrec, qloss, idx
+
+    def forward(self, input):  # VQModel_arch.py:98-101
+        """(dec fp32 NCHW, diff): under grad the taped graph above, under no_grad decode(encode(input))."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            xrec, qloss, _ = self.train_nhwc(input)
+            return A.nhwc_to_nchw(xrec), qloss
+        dec, diff, _ = self.decode(self.encode(input)[0])
+        return dec, diff

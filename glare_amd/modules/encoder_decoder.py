@@ -485,6 +485,25 @@ class Decoder(HipModule):
             img = ops.conv2d(hh, packed_conv(self, self.conv_out), out_mode=ops.OUT_PLANAR_F32).view(B, -1, H, W)
         return img, feats
 
+    def train_nhwc(self, z):
+        """forward_nhwc with a tape (stage-1 training, VQModel_arch.py:98-101): z fp32 NHWC latent, differentiated ->
+        (image fp32 NHWC, [feat@half, feat@full] 16-bit NHWC).  The trunk is MultiScaleDecoder2.train_nhwc's."""
+        assert not self.give_pre_end
+        h = A.conv2d_small(z, self.conv_in.weight, self.conv_in.bias, layout="nhwc")
+        h = self.mid.block_2.train_nhwc(self.mid.attn_1.train_nhwc(self.mid.block_1.train_nhwc(h)))
+        feats = []
+        for i_level in reversed(range(self.num_resolutions)):
+            lvl = self.up[i_level]
+            for i_block in range(self.num_res_blocks + 1):
+                h = lvl.block[i_block].train_nhwc(h)
+                if len(lvl.attn) > 0:
+                    h = lvl.attn[i_block].train_nhwc(h)
+            if i_level != 2:  # encoder_decoder.py:538-539
+                feats.append(h)
+            if i_level != 0:
+                h = lvl.upsample.train_nhwc(h)
+        return conv_t(gn_swish_t(h, self.norm_out), self.conv_out, out_f32=True), feats
+
     def forward(self, z):
         img, feats = self.forward_nhwc(to_nhwc(z, bf16=False))
         return img, [to_nchw(f) for f in feats]

@@ -1,11 +1,15 @@
-"""Codebook retrieval on the HIP nearest-code kernel.
+"""Codebook retrieval on the HIP nearest-code kernel, and its training form.
 
 Mirrors VectorQuantizer2 (code/models/modules/quantize.py:213-329): same constructor, same
 `forward(z) -> (z_q, loss, (perplexity, min_encodings, min_encoding_indices))` contract with
-`sane_index_shape=False` semantics (flat int64 indices), `legacy=False` loss, straight-through z_q."""
+`sane_index_shape=False` semantics (flat int64 indices), both `legacy` orders of the loss, straight-through z_q.
+Without a tape (no_grad, or an input that needs no gradient) the lookup is the inference kernel plus elementwise glue; on an
+input that requires a gradient (stage 1, VQModel.train_nhwc) the loss, the straight-through output and the gradients of the
+latent and of the codebook come from csrc/vq_train.hip through autograd.vq_straight_through."""
 import torch
 import torch.nn as nn
 
+from .. import autograd as A
 from .. import ops
 from ._base import HipModule
 
@@ -28,10 +32,14 @@ class VectorQuantizer2(HipModule):
         assert not rescale_logits and not return_logits
         ops.require_cuda(z)
         if torch.is_grad_enabled() and z.requires_grad:
-            # GLARE only ever runs the codebook under no_grad (VQLLFLOWDeformable_arch.py:245, LLFlow_model.py:200): the HIP
-            # lookup has no tape, so the commitment / codebook losses below could not train anything -- refuse loudly
-            raise NotImplementedError("VectorQuantizer2 on HIP is inference-only (stage-1 VQGAN training is out of scope): "
-                                      "call it under torch.no_grad()")
+            # stage-1 training (VQModel_arch.py:98-101): the same lookup with a tape -- the loss sum, the straight-through output and
+            # both gradients are kernels of csrc/vq_train.hip (autograd.VQStraightThroughFn), bitwise reproducible
+            w_z, w_e = (1.0, self.beta) if self.legacy else (self.beta, 1.0)             # quantize.py:290-295
+            zq, loss, idx = A.vq_straight_through(A.nchw_to_nhwc_f32(z), self.embedding.weight, w_z, w_e)
+            zq = A.nhwc_to_nchw(zq)
+            if self.sane_index_shape:
+                idx = idx.reshape(zq.shape[0], zq.shape[2], zq.shape[3])
+            return zq, loss, (None, None, idx)
         zp = ops.nchw_to_nhwc(z, bf16=False)  # 'b c h w -> b h w c' (quantize.py:276)
         flat = zp.view(-1, self.e_dim)
         idx, zq = self.quantize_tokens(flat)

@@ -1,5 +1,5 @@
-"""Training steps on the HIP path: stage 2 (row a12: conditional encoder + flow, NLL objective) and the data-parallel
-plumbing both stages share.
+"""Training steps on the HIP path: stage 1 (the VQGAN prior: reconstruction + codebook objective), stage 2 (row a12: conditional
+encoder + flow, NLL objective), stage 3 (row a13) and the data-parallel plumbing they share.
 
 Reference: LLFlowModel.optimize_parameters (code/models/LLFlow_model.py:181-250) with its optimizer setup (:90-122):
 torch.optim.Adam over two parameter groups -- the flow ("other", lr_G, weight_decay_G) and the conditional encoder
@@ -267,6 +267,9 @@ class FlatAdam:
 # fuse / scale / shift layers of the unused gating path and its own conv_out (deformableDecoder_arch.py:490-523).
 STAGE2_NEVER_USED = ("flowUpsamplerNet.f.",)
 STAGE3_NEVER_USED = ("deformable_decoder.scale.", "deformable_decoder.bias.", "deformable_decoder.enc.", "deformable_decoder.conv_out.")
+# ... and, in VQModel, the 3 -> 256 conv of the semantic branch: `encode` returns vgg_feat = None (VQModel_arch.py:74-79), so `decode`
+# never calls it (:81-91).
+STAGE1_NEVER_USED = ("conv_semantic.",)
 
 
 class Stage2Trainer:
@@ -381,6 +384,70 @@ class Stage3Trainer:
             self.opt.step()
         G.deformable_decoder.invalidate()   # only its packed inference weights went stale; the frozen nets keep theirs
         return loss.detach()
+
+
+class Stage1Trainer:
+    """One optimisation step of stage 1, the VQGAN prior itself (VQModel.forward + configure_optimizers, VQModel_arch.py:98-101,
+    148-157): x -> encoder -> quant_conv -> codebook (straight-through) -> post_quant_conv -> decoder, every layer with a tape.
+    Loss: mean |xrec - x| + codebook_weight * qloss (+ perceptual_weight * perceptual(xrec, x) when a perceptual network is passed).
+    x is the ground-truth crop in [0, 1] -- what `net_hq.encode` is fed in stages 2 and 3.  The L1 is plain, not `l1_clamp_loss`: a
+    clamp would zero the gradient wherever the reconstruction leaves [0, 1].
+
+    NOT built: the reference's `self.loss` is taming's VQLPIPSWithDiscriminator, which is not part of the reference tree -- neither the
+    patch discriminator (the GAN term) nor LPIPS (pretrained VGG weights, unobtainable offline as in stage 3) exists here, so this
+    trains the reconstruction + codebook objective only.  The optimizer is the reference's: Adam, betas
+    (0.5, 0.9), one group over encoder, decoder, quantize, quant_conv and post_quant_conv (:148-157)."""
+
+    def __init__(self, net, lr_G=1e-4, weight_decay_G=0.0, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0,
+                 device_state=False, precision="fp16"):
+        """lr_G: a starting point, not a tuned value (the reference sets `self.learning_rate` from a config it does not ship).
+        precision: as Stage2Trainer ("fp16" = AMP with the device-resident GradScaler, the default; "bf16" on request)."""
+        from . import autograd as A
+
+        assert precision in ("bf16", "fp16")
+        self.precision, self.A = precision, A
+        self.codebook_weight, self.perceptual, self.perceptual_weight = float(codebook_weight), perceptual, float(perceptual_weight)
+        self.last_terms = {}
+        self.checkpoint_tag = "VQ"                   # glare_amd.fit: <out>/models/<iter>_VQ.pth, the file `--net-vq` takes
+        self.net = self.netG = net.train()           # `netG`: the name the driver and the checkpoint code read
+        for p in net.parameters():
+            p.requires_grad_(True)
+        named = list(net.named_parameters())
+        never = [p for n, p in named if n.startswith(STAGE1_NEVER_USED)]
+        # one group, and an empty second one so that `.state` files have the layout of the other stages
+        self.opt = FlatAdam([FlatGroup([p for _, p in named], lr_G, weight_decay_G, never_used=never),
+                             FlatGroup([], lr_G, 0.0, device=named[0][1].device)], betas=(0.5, 0.9), device_state=device_state,
+                            loss_scaling=precision == "fp16")
+        self.pack_cache = ops.PackCache([p for n, p in named if not n.startswith(STAGE1_NEVER_USED)])
+
+    def step(self, gt_img, lr_img=None):
+        """gt_img: fp32 NCHW ground-truth crop in [0, 1]; lr_img is ignored (the driver hands both halves of a pair).  Returns the loss."""
+        return float(self.step_tensor(gt_img, lr_img))
+
+    def step_tensor(self, gt_img, lr_img=None):
+        """The step without any host synchronisation: returns the loss as a device tensor."""
+        gt = gt_img.float().contiguous()
+        with ops.use_precision(self.precision):
+            self.opt.zero_grad()
+            with self.pack_cache:
+                xrec, qloss, _ = self.net.train_nhwc(gt)
+                loss, self.last_terms = stage1_loss(xrec, gt, qloss, self.codebook_weight, self.perceptual, self.perceptual_weight)
+                self.opt.scale_loss(loss).backward()
+            self.opt.step()
+        self.net.invalidate()                        # packed inference weights are stale now
+        return loss.detach()
+
+
+def stage1_loss(xrec_nhwc, gt_nchw, qloss, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0):
+    """total = mean |xrec - x| + codebook_weight * qloss (+ perceptual_weight * perceptual(xrec, x)) on the NHWC fp32 reconstruction.
+    Returns (total, {term: float-able tensor})."""
+    from . import autograd as A
+    from . import ops
+
+    terms = {"l1_loss": A.l1_loss(xrec_nhwc, gt_nchw), "codebook_loss": qloss * codebook_weight}
+    if perceptual is not None:
+        terms["percep_loss"] = perceptual(xrec_nhwc, ops.nchw_to_nhwc(gt_nchw, bf16=False)) * perceptual_weight
+    return sum(terms.values()), terms
 
 
 def stage3_loss(rec_nhwc, gt_nchw, perceptual=None, use_msssim=True):

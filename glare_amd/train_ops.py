@@ -395,6 +395,20 @@ def l1_clamp_loss(rec_nhwc, gt_nchw):
     return loss, grad
 
 
+def l1_loss(rec_nhwc, gt_nchw):
+    """-> (loss fp32 [1], grad fp32 NHWC) of the plain mean |rec - gt| (stage 1)."""
+    require_cuda(rec_nhwc, gt_nchw)
+    assert rec_nhwc.dtype == gt_nchw.dtype == torch.float32 and rec_nhwc.is_contiguous() and gt_nchw.is_contiguous()
+    B, H, W, C = rec_nhwc.shape
+    assert tuple(gt_nchw.shape) == (B, C, H, W)
+    loss = torch.empty(1, dtype=torch.float32, device=rec_nhwc.device)
+    grad = torch.empty_like(rec_nhwc)
+    ws = torch.empty(512, dtype=torch.float32, device=rec_nhwc.device)
+    check(_lib.lib().glare_l1_loss_f32(ptr(rec_nhwc), ptr(gt_nchw), B, H * W, C, ptr(loss), ptr(grad), ptr(ws), 2048, stream_handle()),
+          "glare_l1_loss_f32")
+    return loss, grad
+
+
 # ---- stage-3 loss stack (row f1) ------------------------------------------------------------------------
 def clamp01(x):
     require_cuda(x)
@@ -649,3 +663,38 @@ def conv1x1_weight_grad(x, g16, cout, cin=None, in_off=0):
     cin = x.shape[-1] - in_off if cin is None else cin
     dwt = conv_weight_grad_nhwc(1, x, g16, cout, cin, in_off)[0]
     return dwt[:cin].t().unsqueeze(-1).unsqueeze(-1), dwt[cin]
+
+
+# ---- the codebook layer's training form (csrc/vq_train.hip; quantize.py:289-298) ----------------------------------------
+def vq_loss_sum(z_tokens, zq_tokens, want_st=True):
+    """z, z_q fp32 [N, 3] -> (S = sum (z_q - z)^2 as fp32 [1], z + (z_q - z) fp32 [N, 3] or None); S in a fixed two-level order."""
+    require_cuda(z_tokens, zq_tokens)
+    assert z_tokens.dtype == torch.float32 and zq_tokens.dtype == torch.float32 and z_tokens.is_contiguous() and zq_tokens.is_contiguous()
+    assert z_tokens.shape == zq_tokens.shape
+    n, dim = z_tokens.shape
+    lib = _lib.lib()
+    nws = lib.glare_vq_train_workspace_bytes(n, 1)
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=z_tokens.device)
+    s = torch.empty(1, dtype=torch.float32, device=z_tokens.device)
+    st = torch.empty_like(z_tokens) if want_st else None
+    check(lib.glare_vq_loss_sum_f32(ptr(z_tokens), ptr(zq_tokens), n, dim, ptr(st), ptr(s), ptr(ws), nws, stream_handle()),
+          "glare_vq_loss_sum_f32")
+    return s, st
+
+
+def vq_backward(z_tokens, zq_tokens, idx, g, gl, n_codes, w_z, w_e, want_dz=True, want_de=True):
+    """-> (dz fp32 [N, 3] or None, dE fp32 [n_codes, 3] or None): dz = g + gl (2 w_z / 3N) (z - z_q), dE[k] = gl (2 w_e / 3N) sum over the
+    tokens of code k of (z_q - z) in a fixed order.  g: gradient of the straight-through output or None; gl: fp32 [1] on the device."""
+    require_cuda(z_tokens, zq_tokens, idx, g, gl)
+    assert z_tokens.dtype == torch.float32 and zq_tokens.dtype == torch.float32 and z_tokens.is_contiguous() and zq_tokens.is_contiguous()
+    assert idx.dtype == torch.int64 and idx.is_contiguous() and gl.dtype == torch.float32 and gl.numel() == 1
+    assert g is None or (g.dtype == torch.float32 and g.is_contiguous() and g.shape == z_tokens.shape)
+    n, dim = z_tokens.shape
+    lib = _lib.lib()
+    nws = lib.glare_vq_train_workspace_bytes(n, n_codes)
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=z_tokens.device)
+    dz = torch.empty_like(z_tokens) if want_dz else None
+    de = torch.empty(n_codes, dim, dtype=torch.float32, device=z_tokens.device) if want_de else None
+    check(lib.glare_vq_backward_f32(ptr(z_tokens), ptr(zq_tokens), ptr(idx), ptr(g), ptr(gl), n, n_codes, dim, 2.0 * w_z / (dim * n),
+                                    2.0 * w_e / (dim * n), ptr(dz), ptr(de), ptr(ws), nws, stream_handle()), "glare_vq_backward_f32")
+    return dz, de

@@ -57,6 +57,28 @@ int glare_vq_nearest_f32(const float* z_nhwc, const float* codebook, long long n
                          int n_codes, int dim, long long* idx_i64, float* zq_nhwc,
                          glare_stream_t stream);
 
+/* ---- a5, training form: the codebook layer of stage 1 (VQGAN prior) -----------------------------
+ * Replaces the loss and the straight-through estimator of VectorQuantizer2.forward
+ * (code/models/modules/quantize.py:289-298) and the gradients autograd derives from them.  All fp32, tokens
+ * token-major [n_tokens][3] as glare_vq_nearest_f32 reads and writes them; idx / zq are ITS outputs.
+ *   S      = sum_i sum_c (zq[i][c] - z[i][c])^2            loss = (w_z + w_e) * S / (3 N)   (quantize.py:290-295;
+ *            (w_z, w_e) = (beta, 1), legacy: (1, beta) -- the caller's scalars)
+ *   zq_st  = z + (zq - z)                                  (quantize.py:298)
+ *   dz[i]  = g[i] + gl * cz * (z[i] - zq[i])               cz = 2 w_z / (3 N); g = gradient of zq_st (NULL: zero)
+ *   dE[k]  = gl * ce * sum_{i: idx[i] = k} (zq[i] - z[i])  ce = 2 w_e / (3 N); a code no token selected gets exactly 0
+ * gl_dev: the upstream gradient of the loss, ONE fp32 on the device (no host read).  No atomics: every sum has a fixed
+ * order that depends on (n_tokens, n_codes) alone, so S, dz and dE are bitwise reproducible.  dE is a fixed-order
+ * per-code sum (token axis in <= 32 segments, partial sums added in segment order); no address depends on an index,
+ * an index outside [0, n_codes) selects nothing.  64-bit token offsets.  dim must be 3.
+ * workspace: glare_vq_train_workspace_bytes(n_tokens, n_codes) bytes of scratch, caller-owned (both entries).
+ * zq_st_nhwc, dz_nhwc or dE may be NULL (not produced; dz and dE not both). */
+size_t glare_vq_train_workspace_bytes(long long n_tokens, int n_codes);
+int glare_vq_loss_sum_f32(const float* z_nhwc, const float* zq_nhwc, long long n_tokens, int dim, float* zq_st_nhwc,
+                          float* loss_sum, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+int glare_vq_backward_f32(const float* z_nhwc, const float* zq_nhwc, const long long* idx_i64, const float* g_nhwc,
+                          const float* gl_dev, long long n_tokens, int n_codes, int dim, float cz, float ce, float* dz_nhwc,
+                          float* dE, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+
 /* ---- a1/a6/a8: im2col-free direct convolution on bf16 MFMA ----------------------------------
  * Replaces torch.nn.Conv2d / F.conv2d for the 3x3 and 1x1 convolutions of the VQGAN
  * encoder/decoder, AttnBlock projections, WarpBlock.offset, DCNv2Pack.conv_offset and the flow
@@ -707,6 +729,10 @@ int glare_sigmoid_f32(const float* x, float* y, long long n, glare_stream_t stre
  * workspace >= 512 floats.  (The VGG-perceptual and MS-SSIM terms of :219-220 are SURVEY.md row f1, not built.) */
 int glare_l1_clamp_loss_f32(const float* rec_nhwc, const float* gt_nchw, int B, long long HW, int C, float* loss_out,
                             float* grad_nhwc, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+/* Stage-1 pixel loss (the reconstruction term of the VQGAN prior's objective): *loss_out = mean |rec - gt|, grad = sign(rec - gt) / n,
+ * no clamp.  Layouts and workspace as glare_l1_clamp_loss_f32. */
+int glare_l1_loss_f32(const float* rec_nhwc, const float* gt_nchw, int B, long long HW, int C, float* loss_out,
+                      float* grad_nhwc, void* workspace, size_t workspace_bytes, glare_stream_t stream);
 
 /* ---- a14 / f2: the inference harness' pre- and post-processing on the device (code/infer_dataset_lol.py:113-153) ------
  * pre : uint8 HWC [B][H][W][3] -> fp32 NCHW [B][3][H+pad][W+pad]: reflect pad bottom / left (impad :71-72), /255 (t :42),
