@@ -186,6 +186,9 @@ int fb_blocks(long long items, int cap) {
 
 #define ST(s) static_cast<hipStream_t>(s)
 
+// Sizes the grid for flow_h1_bwd_kernel's 8 threads per pixel.  flow_pre_bwd_kernel is launched on the same grid with ONE thread per
+// pixel, so below 65536 pixels only the first ceil(n_pixels / 256) of its blocks own a pixel and the rest write zero partials.  Kept:
+// another grid would change which block sums which pixels, i.e. the summation order of gM / gt.
 extern "C" int glare_flow_bwd_blocks(long long n_pixels) { return fb_blocks(n_pixels * 8, 256); }
 
 extern "C" int glare_flow_nll_backward_f32(const float* z, const float* mean, const float* g_logp_per_sample, int B,
