@@ -556,3 +556,111 @@ class ForkFn(torch.autograd.Function):
 
 def fork(x, n=2):
     return ForkFn.apply(x, n)
+
+
+# ---- the patch discriminator of the stage-1 GAN term ------------------------------------------------------------------------------------
+# The generator's GAN term needs d g_loss / d xrec THROUGH the discriminator but none of the discriminator's parameter gradients (its
+# parameters receive no update from that loss): under `data_grad_only()` the discriminator's nodes skip their weight / affine gradients.
+# A plain module flag, not a thread-local: backward runs on the autograd engine's own thread while the caller waits inside the `with`.
+_DATA_GRAD_ONLY = False
+
+
+class data_grad_only:
+    def __enter__(self):
+        global _DATA_GRAD_ONLY
+        self._prev, _DATA_GRAD_ONLY = _DATA_GRAD_ONLY, True
+        return self
+
+    def __exit__(self, *exc):
+        global _DATA_GRAD_ONLY
+        _DATA_GRAD_ONLY = self._prev
+
+
+@_lib.keeps_precision
+class Conv4x4Fn(torch.autograd.Function):
+    """y = [LeakyReLU(0.2)](conv(x; 4x4, pad 1, stride 1 | 2) + bias): x NHWC 16-bit, or fp32 for the 3-channel image in front of layer 1
+    (its data gradient is then fp32 too); weight OIHW fp32.  Saves nothing the backward mutates: retain_graph=True is supported."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, lrelu, out_f32):
+        x = x.contiguous()
+        y = T.conv4x4_forward(x, weight, bias, stride=stride, lrelu=lrelu, out_f32=out_f32)
+        assert not (lrelu and out_f32)
+        ctx.cfg = (stride, lrelu, bias is not None)
+        ctx.save_for_backward(x, weight, y if lrelu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        stride, lrelu, has_bias = ctx.cfg
+        x, weight, y = ctx.saved_tensors
+        cout, cin = weight.shape[:2]
+        cp = _rup(cout, 8)
+        g = gy.contiguous()
+        if g.dtype == torch.float32:
+            g = T.cast_to_bf16(g, pitch=cout if lrelu else cp)
+        if lrelu:
+            g = T.lrelu_backward(g, y)
+        if g.shape[-1] != cp:
+            g = T.cast_to_bf16(T.cast_to_f32(g), pitch=cp)
+        dw = db = dx = None
+        if (ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])) and not _DATA_GRAD_ONLY:
+            dwb = T.conv4x4_weight_grad(x, g, cout, stride)
+            dw = dwb[:, :-1].unflatten(1, (cin, 4, 4))
+            db = dwb[:, -1] if has_bias else None
+        if ctx.needs_input_grad[0]:
+            dx = T.conv4x4_dgrad(g, weight, tuple(x.shape), stride=stride, out_f32=x.dtype == torch.float32)
+        return dx, dw, db, None, None, None
+
+
+def conv4x4(x, weight, bias=None, stride=2, lrelu=False, out_f32=False):
+    return Conv4x4Fn.apply(x, weight, bias, stride, lrelu, out_f32)
+
+
+@_lib.keeps_precision
+class BatchNormLReLUFn(torch.autograd.Function):
+    """nn.BatchNorm2d in training mode [+ LeakyReLU(0.2)] on 16-bit NHWC; `groups`: statistics per run of B / groups consecutive images.
+    The running buffers are updated in place by the forward, as the module's forward does."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, num_batches_tracked, groups, lrelu, eps, momentum):
+        x = x.contiguous()
+        y, saved = T.batchnorm_forward(x, gamma, beta, groups=groups, lrelu=lrelu, eps=eps, momentum=momentum, running_mean=running_mean,
+                                       running_var=running_var, num_batches_tracked=num_batches_tracked)
+        ctx.cfg = (groups, lrelu)
+        ctx.save_for_backward(x, saved, gamma, beta)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        groups, lrelu = ctx.cfg
+        x, saved, gamma, beta = ctx.saved_tensors
+        dx, dgamma, dbeta = T.batchnorm_backward(x, gy.contiguous(), saved, gamma, beta, groups=groups, lrelu=lrelu)
+        if _DATA_GRAD_ONLY:
+            dgamma = dbeta = None
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def batchnorm_lrelu(x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, groups=1, lrelu=True, eps=1e-5,
+                    momentum=0.1):
+    return BatchNormLReLUFn.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, groups, lrelu, eps, momentum)
+
+
+@_lib.keeps_precision
+class HingeLossFn(torch.autograd.Function):
+    """The GAN term's reductions over fp32 logits: "real" mean relu(1 - x), "fake" mean relu(1 + x), "generator" -mean x."""
+
+    @staticmethod
+    def forward(ctx, x, mode):
+        loss, grad = T.hinge_loss(x.contiguous(), mode)
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None     # a logit-map-sized (1-channel) scale by the scalar upstream gradient, as L1LossFn
+
+
+def hinge_loss(x, mode):
+    return HingeLossFn.apply(x, mode)

@@ -52,6 +52,8 @@ DEFAULTS = {
                "train": dict(_COMMON_TRAIN, lr_G=5e-5, niter=40000),
                "logger": {"print_freq": 5, "save_checkpoint_freq": 500}},
 }
+DISC_KEY = "discriminator"   # --gan: {"optimizer": Adam state dict, "scaler": GradScaler state dict} of the discriminator
+GAN_TERMS = ("g_loss", "d_weight", "d_loss")
 STATE_KEY = "glare_fit"      # the extra key of a `.state` file: RNG states and the place in the epoch (the reference ignores it)
 STEADY_FROM = 20             # the closing summary's ms per step leaves out this many steps
 
@@ -210,6 +212,7 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
     sched = make_schedule(trainer.opt, options)
     set_random_seed(tr["manual_seed"])
     epoch, step, order, done = 0, 0, None, 0
+    gan = getattr(trainer, "discriminator", None) is not None      # stage 1 with --gan: D's weights, optimizer and scaler travel too
     if resume:
         st = torch.load(resume, map_location="cpu", weights_only=False) if isinstance(resume, str) else resume
         epoch, step = checkpoint.resume_training(st, trainer, [sched])
@@ -217,15 +220,25 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
         if STATE_KEY in st:                  # written by this driver: continue the exact index / augmentation sequence
             _set_rng_state(st[STATE_KEY]["rng"])
             order, done = st[STATE_KEY]["epoch_order"], st[STATE_KEY]["batches_done"]
+        if hasattr(trainer, "global_step"):
+            trainer.global_step = step       # what `disc_start` is compared with
+        if gan:
+            assert DISC_KEY in st, "--gan: the .state file carries no discriminator optimizer (it was written without --gan)"
+            checkpoint.load_adam_state_dict(trainer.opt_d, st[DISC_KEY]["optimizer"])
+            trainer.opt_d.load_scaler_state_dict(st[DISC_KEY]["scaler"])
 
     tag = getattr(trainer, "checkpoint_tag", "G")        # stage 1 writes <iter>_VQ.pth: the file `--net-vq` takes
 
     def save(epoch, step, order, done):
         checkpoint.save_network(trainer.netG, os.path.join(out_dir, "models", "%d_%s.pth" % (step, tag)))
+        extra = {STATE_KEY: {"rng": _rng_state(), "epoch_order": order, "batches_done": done}}
+        if gan:      # <iter>_D.pth: taming's NLayerDiscriminator state dict; its Adam and GradScaler state as one more key of the .state file
+            checkpoint.save_network(trainer.discriminator, os.path.join(out_dir, "models", "%d_D.pth" % step))
+            extra[DISC_KEY] = {"optimizer": checkpoint.adam_state_dict(trainer.opt_d), "scaler": trainer.opt_d.scaler_state_dict()}
         sched._swap_in_current()
         try:
             checkpoint.save_training_state(os.path.join(out_dir, "training_state", "%d.state" % step), trainer, epoch, step, [sched],
-                                           extra={STATE_KEY: {"rng": _rng_state(), "epoch_order": order, "batches_done": done}})
+                                           extra=extra)
         finally:
             sched._swap_in_base()
 
@@ -250,6 +263,8 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
                 now = time.perf_counter()
                 rec = {"epoch": epoch, "iter": step, "lr": lr, "loss": loss, "ms_per_step": 1e3 * (now - t_win) / n_win,
                        "ms_batch": 1e3 * t_batch / n_win}
+                if gan:
+                    rec.update((k, float(trainer.last_terms[k])) for k in GAN_TERMS)
             if step - first == STEADY_FROM:
                 _sync()
                 t_steady = time.perf_counter()
@@ -275,8 +290,9 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
 
 
 # ---- the command ---------------------------------------------------------------------------------------------------------------
-def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16"):
-    """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer."""
+def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16", gan=False, net_d=None):
+    """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer.  gan (stage 1 only): with the
+    patch discriminator (taming's initialisation under the run's seed, or the `_D.pth` file net_d)."""
     from . import modules as M
     from .synthetic import seeded_init_
     from .train import Stage1Trainer, Stage2Trainer, Stage3Trainer
@@ -288,8 +304,19 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
         net = seeded_init_(M.VQModel().train(), 1)
         if net_vq:
             checkpoint.load_network(net_vq, net, strict=False)
+        disc = None
+        if gan:
+            set_random_seed(tr["manual_seed"])       # N(0, 0.02) / N(1, 0.02): the same discriminator for the same seed
+            disc = M.NLayerDiscriminator()
+            if net_d:
+                checkpoint.load_network(net_d, disc, strict=True)
+            disc = disc.to(device)
         return Stage1Trainer(net.to(device), lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0),
-                             codebook_weight=tr.get("codebook_weight", 1.0), precision=precision)
+                             codebook_weight=tr.get("codebook_weight", 1.0), precision=precision, discriminator=disc,
+                             disc_start=tr.get("disc_start", 10000), disc_weight=tr.get("disc_weight", 0.8),
+                             disc_factor=tr.get("disc_factor", 1.0))
+    if gan:
+        raise ValueError(GAN_REFUSAL)
     net_hq = seeded_init_(M.VQModel().eval(), 1)
     if stage == "stage2":
         netG = seeded_init_(M.LLFlowVQGAN2(opt=options).train(), 2)
@@ -306,6 +333,7 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
     return Stage3Trainer(netG, net_hq, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0), device_state=graph, precision=precision)
 
 
+GAN_REFUSAL = "--gan is a stage1 option: the patch discriminator belongs to the VQGAN prior's objective (stages 2 and 3 train no GAN term)"
 GRAPH_REFUSAL = "--graph is not available for stage1: its step is not captured into a hipGraph (GraphedStep covers stages 2 and 3)"
 
 
@@ -401,16 +429,24 @@ def parse_args(argv=None):
     ap.add_argument("--net-vq", default=None, help="VQGAN checkpoint (reference format); stage1: the weights to start from")
     ap.add_argument("--graph", action="store_true", help="replay the step from a hipGraph (GraphedStep; stages 2 and 3)")
     ap.add_argument("--precision", choices=("fp16", "bf16"), default="fp16")
+    ap.add_argument("--gan", action="store_true", help="stage1: add the patch discriminator (hinge loss, adaptive weight); writes <iter>_D.pth")
+    ap.add_argument("--disc-start", type=int, default=None, help="--gan: first step whose loss has the GAN term (default 10000)")
+    ap.add_argument("--disc-weight", type=float, default=None, help="--gan: factor on the adaptive weight (default 0.8)")
     ap.add_argument("--no-val", action="store_true", help="skip the closing validation")
     args = ap.parse_args(argv)
     if args.graph and args.stage == "stage1":
         ap.error(GRAPH_REFUSAL)
+    if args.gan and args.stage != "stage1":
+        ap.error(GAN_REFUSAL)
+    if not args.gan and (args.disc_start is not None or args.disc_weight is not None):
+        ap.error("--disc-start / --disc-weight need --gan")
 
     options = default_options(args.stage)
     if args.opt:
         merge_options(options, load_options_file(args.opt))
     for value, (section, key) in ((args.niter, ("train", "niter")), (args.val_freq, ("train", "val_freq")),
-                                  (args.save_freq, ("logger", "save_checkpoint_freq"))):
+                                  (args.save_freq, ("logger", "save_checkpoint_freq")), (args.disc_start, ("train", "disc_start")),
+                                  (args.disc_weight, ("train", "disc_weight"))):
         if value is not None:
             options[section][key] = value
     if args.batch is not None:
@@ -424,19 +460,20 @@ def main(argv=None):
     args, options = parse_args(argv)
     assert torch.cuda.is_available(), "glare_amd.fit needs an MI355X: the HIP kernels are the only implementation"
     device = torch.device("cuda", 0)
-    net_g, net_vq = args.net_g, args.net_vq
+    net_g, net_vq, net_d = args.net_g, args.net_vq, None
     resume = None
     if args.resume:
         resume = torch.load(args.resume, map_location="cpu", weights_only=False)
         models = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(args.resume))), "models")
         if args.stage == "stage1":
             net_vq = net_vq or os.path.join(models, "%d_VQ.pth" % resume["iter"])
+            net_d = os.path.join(models, "%d_D.pth" % resume["iter"]) if args.gan else None
         elif net_g is None:
             net_g = os.path.join(models, "%d_G.pth" % resume["iter"])
     train_opt = dict(options["datasets"]["train"], root=args.root)
     host_ds = D.LAYOUTS[args.layout](train_opt, train=True, all_opt=options)
     dataset = D.DeviceLoLDataset(host_ds, device)
-    trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision)
+    trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision, gan=args.gan, net_d=net_d)
     step_fn, batch_fn = graphed_fns(trainer, dataset) if args.graph else (None, None)
     validate_fn = None
     # stage 3 scores the inference path, stage 1 the prior's own reconstruction of the ground truth; stage 2 has nothing to score

@@ -393,15 +393,28 @@ class Stage1Trainer:
     x is the ground-truth crop in [0, 1] -- what `net_hq.encode` is fed in stages 2 and 3.  The L1 is plain, not `l1_clamp_loss`: a
     clamp would zero the gradient wherever the reconstruction leaves [0, 1].
 
-    NOT built: the reference's `self.loss` is taming's VQLPIPSWithDiscriminator, which is not part of the reference tree -- neither the
-    patch discriminator (the GAN term) nor LPIPS (pretrained VGG weights, unobtainable offline as in stage 3) exists here, so this
-    trains the reconstruction + codebook objective only.  The optimizer is the reference's: Adam, betas
-    (0.5, 0.9), one group over encoder, decoder, quantize, quant_conv and post_quant_conv (:148-157)."""
+    The reference's `self.loss` is taming's VQLPIPSWithDiscriminator (`self.loss(qloss, x, xrec, optimizer_idx, global_step,
+    last_layer=self.get_last_layer())`, VQModel_arch.py:110-160), which is not part of the reference tree.  Of its three parts LPIPS is
+    NOT built (pretrained VGG weights, unobtainable offline as in stage 3); the patch discriminator with the hinge loss and the adaptive
+    weight are, behind `discriminator=`.  With a discriminator D the step at global step t is
+        nll      = l1 (+ perceptual)                       g_loss = -mean D(xrec)
+        d_weight = clamp(|d nll / d W_last| / (|d g_loss / d W_last| + 1e-4), 0, 1e4) * disc_weight, detached; W_last = decoder.conv_out.weight
+        loss     = nll + d_weight f g_loss + codebook_weight qloss            f = disc_factor if t >= disc_start else 0
+        d_loss   = f 0.5 (mean relu(1 - D(x)) + mean relu(1 + D(xrec.detach())))          D's own Adam (betas (0.5, 0.9), lr_G) and GradScaler
+    from ONE pass through D over [x; xrec] as two batch groups (BatchNorm statistics per half, as two calls): the fake half's logits
+    serve g_loss and d_loss alike, the generator's term takes only the data gradient of that pass (autograd.data_grad_only), D's term only
+    its parameter gradients.  Both gradients at xrec are pushed through conv_out's weight gradient once each for the two norms and the
+    generator is backpropagated ONCE from their weighted sum -- the arithmetic of the reference's two backward passes.  D sees the xrec of
+    this step's generator forward (Lightning's loop runs the generator forward again after its update).  While t < disc_start nothing of D
+    is launched and the generator's update is today's, bit for bit.  The optimizer is the reference's: Adam, betas (0.5, 0.9), one group
+    over encoder, decoder, quantize, quant_conv and post_quant_conv (:148-157)."""
 
     def __init__(self, net, lr_G=1e-4, weight_decay_G=0.0, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0,
-                 device_state=False, precision="fp16"):
+                 device_state=False, precision="fp16", discriminator=None, disc_start=10000, disc_weight=0.8, disc_factor=1.0):
         """lr_G: a starting point, not a tuned value (the reference sets `self.learning_rate` from a config it does not ship).
-        precision: as Stage2Trainer ("fp16" = AMP with the device-resident GradScaler, the default; "bf16" on request)."""
+        precision: as Stage2Trainer ("fp16" = AMP with the device-resident GradScaler, the default; "bf16" on request).
+        discriminator: an NLayerDiscriminator on the net's device, or None (no GAN term: the step and every file are what they were);
+        disc_start / disc_weight / disc_factor: taming's defaults for the VQGAN configs."""
         from . import autograd as A
 
         assert precision in ("bf16", "fp16")
@@ -419,6 +432,21 @@ class Stage1Trainer:
                              FlatGroup([], lr_G, 0.0, device=named[0][1].device)], betas=(0.5, 0.9), device_state=device_state,
                             loss_scaling=precision == "fp16")
         self.pack_cache = ops.PackCache([p for n, p in named if not n.startswith(STAGE1_NEVER_USED)])
+        self.discriminator, self.opt_d = discriminator, None
+        self.disc_start, self.disc_weight, self.disc_factor = int(disc_start), float(disc_weight), float(disc_factor)
+        self.global_step = 0                         # Lightning's global_step: steps taken so far (the driver restores it on resume)
+        if discriminator is not None:
+            discriminator.train()
+            for p in discriminator.parameters():
+                p.requires_grad_(True)
+            dparams = list(discriminator.parameters())
+            self.opt_d = FlatAdam([FlatGroup(dparams, lr_G, 0.0), FlatGroup([], lr_G, 0.0, device=dparams[0].device)], betas=(0.5, 0.9),
+                                  device_state=device_state, loss_scaling=precision == "fp16")
+            self._zero = torch.zeros((), dtype=torch.float32, device=dparams[0].device)
+
+    def get_last_layer(self):
+        """VQModel.get_last_layer (VQModel_arch.py:159-160): the weight the adaptive GAN weight takes its two gradient norms at."""
+        return self.net.decoder.conv_out.weight
 
     def step(self, gt_img, lr_img=None):
         """gt_img: fp32 NCHW ground-truth crop in [0, 1]; lr_img is ignored (the driver hands both halves of a pair).  Returns the loss."""
@@ -427,6 +455,9 @@ class Stage1Trainer:
     def step_tensor(self, gt_img, lr_img=None):
         """The step without any host synchronisation: returns the loss as a device tensor."""
         gt = gt_img.float().contiguous()
+        t, self.global_step = self.global_step, self.global_step + 1
+        if self.discriminator is not None and t >= self.disc_start and self.disc_factor != 0.0:
+            return self._gan_step(gt)
         with ops.use_precision(self.precision):
             self.opt.zero_grad()
             with self.pack_cache:
@@ -435,7 +466,73 @@ class Stage1Trainer:
                 self.opt.scale_loss(loss).backward()
             self.opt.step()
         self.net.invalidate()                        # packed inference weights are stale now
+        if self.discriminator is not None:           # before disc_start: f = 0, nothing of D launched, its parameters and optimizer untouched
+            self.last_terms.update(g_loss=self._zero, d_weight=self._zero, d_loss=self._zero)
         return loss.detach()
+
+    def _disc_logits(self, gt_nchw, xrec_nhwc):
+        """One pass of D over [x; xrec] as two batch groups -> (logits of the real half, of the fake half), fp32 [B, oh, ow, 1]."""
+        both = torch.cat([ops.nchw_to_nhwc(gt_nchw, bf16=False), xrec_nhwc])      # 3-channel images: an image-sized copy
+        logits = self.discriminator.train_nhwc(both, groups=2)
+        B = gt_nchw.shape[0]
+        return logits[:B], logits[B:]
+
+    def _gan_step(self, gt):
+        A, D = self.A, self.discriminator
+        f = self.disc_factor
+        with ops.use_precision(self.precision):
+            self.opt.zero_grad()
+            self.opt_d.zero_grad()
+            self.opt_d.state3[2:3].copy_(self.opt.state3[2:3])       # D's lr follows the generator's schedule (one device scalar)
+            with self.pack_cache:
+                xrec, qloss, _ = self.net.train_nhwc(gt)
+                # the two gradients at xrec, on a detached leaf: nll's and, through D (data gradients only), g_loss's.  Both carry the
+                # generator's loss scale s (fp16: 1 / n of a mean is an fp16 subnormal unscaled), divided out of the norms below
+                xr = xrec.detach().requires_grad_(True)
+                nll, terms = stage1_loss(xr, gt, None, self.codebook_weight, self.perceptual, self.perceptual_weight)
+                s = self.opt.scale.reshape(()) if self.opt.loss_scaling else None
+                scaled = (lambda v: v * s) if s is not None else (lambda v: v)
+                (g_nll,) = torch.autograd.grad(scaled(nll), xr)
+                logits_real, logits_fake = self._disc_logits(gt, xr)
+                g_loss = A.hinge_loss(logits_fake, "generator")
+                with A.data_grad_only():
+                    (g_gan,) = torch.autograd.grad(scaled(g_loss), xr, retain_graph=True)
+                w_last = self.get_last_layer()
+                (dw_nll,) = torch.autograd.grad(xrec, w_last, grad_outputs=g_nll, retain_graph=True)
+                (dw_gan,) = torch.autograd.grad(xrec, w_last, grad_outputs=g_gan, retain_graph=True)
+                n_nll, n_gan = dw_nll.float().norm(), dw_gan.float().norm()
+                if s is not None:
+                    n_nll, n_gan = n_nll / s, n_gan / s
+                d_weight = (n_nll / (n_gan + 1e-4)).clamp(0.0, 1e4).detach() * self.disc_weight
+                cb = qloss * self.codebook_weight
+                # one backward of the generator from the weighted sum of the two gradients at xrec, and the codebook term
+                torch.autograd.backward([xrec, scaled(cb)], [g_nll + (d_weight * f) * g_gan, None])
+                # the discriminator: parameter gradients only, from the same pass
+                d_loss = (A.hinge_loss(logits_real, "real") + A.hinge_loss(logits_fake, "fake")) * (0.5 * f)
+                torch.autograd.backward(self.opt_d.scale_loss(d_loss), inputs=self.opt_d.groups[0].params)
+            self.opt.step()
+            self.opt_d.step()
+        self.net.invalidate()
+        D.invalidate()
+        loss = nll.detach() + d_weight * f * g_loss.detach() + cb.detach()
+        terms["codebook_loss"] = cb
+        terms.update(g_loss=g_loss.detach(), d_weight=d_weight, d_loss=d_loss.detach())
+        self.last_terms = terms
+        return loss
+
+    def discriminator_step(self, gt_img, xrec_nhwc):
+        """One update of D alone on (x, a given reconstruction): d_loss = disc_factor 0.5 (mean relu(1 - D(x)) + mean relu(1 + D(xrec))).
+        The generator is not touched.  Returns d_loss as a device tensor."""
+        gt = gt_img.float().contiguous()
+        with ops.use_precision(self.precision):
+            self.opt_d.zero_grad()
+            logits_real, logits_fake = self._disc_logits(gt, xrec_nhwc.detach().float().contiguous())
+            d_loss = (self.A.hinge_loss(logits_real, "real") + self.A.hinge_loss(logits_fake, "fake")) * (0.5 * self.disc_factor)
+            self.opt_d.scale_loss(d_loss).backward()
+            self.opt_d.step()
+        self.discriminator.invalidate()
+        self.last_logits = (logits_real.detach(), logits_fake.detach())
+        return d_loss.detach()
 
 
 def stage1_loss(xrec_nhwc, gt_nchw, qloss, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0):
@@ -444,7 +541,9 @@ def stage1_loss(xrec_nhwc, gt_nchw, qloss, codebook_weight=1.0, perceptual=None,
     from . import autograd as A
     from . import ops
 
-    terms = {"l1_loss": A.l1_loss(xrec_nhwc, gt_nchw), "codebook_loss": qloss * codebook_weight}
+    terms = {"l1_loss": A.l1_loss(xrec_nhwc, gt_nchw)}
+    if qloss is not None:                # None: the reconstruction terms alone (the GAN step's nll)
+        terms["codebook_loss"] = qloss * codebook_weight
     if perceptual is not None:
         terms["percep_loss"] = perceptual(xrec_nhwc, ops.nchw_to_nhwc(gt_nchw, bf16=False)) * perceptual_weight
     return sum(terms.values()), terms

@@ -698,3 +698,140 @@ def vq_backward(z_tokens, zq_tokens, idx, g, gl, n_codes, w_z, w_e, want_dz=True
     check(lib.glare_vq_backward_f32(ptr(z_tokens), ptr(zq_tokens), ptr(idx), ptr(g), ptr(gl), n, n_codes, dim, 2.0 * w_z / (dim * n),
                                     2.0 * w_e / (dim * n), ptr(dz), ptr(de), ptr(ws), nws, stream_handle()), "glare_vq_backward_f32")
     return dz, de
+
+
+# ---- the patch discriminator of the stage-1 GAN term (csrc/conv4x4.hip, csrc/disc_ops.hip) --------------------------------------------
+def conv4x4_out(size, stride):
+    """Output side of the 4x4 / pad 1 conv: (size - 2) // stride + 1."""
+    return (size + 2 - 4) // stride + 1
+
+
+def conv4x4_pack(weight, dgrad=False):
+    """fp32 OIHW [Cout, Cin, 4, 4] -> the packed 16-bit filter of the forward (dgrad=False) or the data-gradient launch."""
+    require_cuda(weight)
+    w = weight.detach().float().contiguous()
+    cout, cin, kh, kw = w.shape
+    assert kh == kw == 4
+    lib = _lib.lib()
+    out = torch.empty(lib.glare_conv4x4_packed_elems(cout, cin, int(dgrad)), dtype=act_dtype(), device=w.device)
+    check(lib.glare_conv4x4_pack_bf16(ptr(w), cout, cin, int(dgrad), ptr(out), stream_handle()), "glare_conv4x4_pack_bf16")
+    return out
+
+
+def conv4x4_forward(x, weight, bias=None, stride=2, lrelu=False, out_f32=False):
+    """y = [LeakyReLU(0.2)](conv4x4(x; pad 1, stride) + bias); x NHWC 16-bit or fp32 (the reconstruction in front of layer 1), weight
+    fp32 OIHW; y NHWC 16-bit (fp32 with out_f32)."""
+    require_cuda(x, weight, bias)
+    assert x.dtype in (act_dtype(), torch.float32) and x.is_contiguous() and x.dim() == 4
+    B, H, W, cin = x.shape
+    cout = weight.shape[0]
+    assert weight.shape[1] == cin and stride in (1, 2)
+    OH, OW = conv4x4_out(H, stride), conv4x4_out(W, stride)
+    assert OH > 0 and OW > 0, "a %dx%d input leaves no output pixel" % (H, W)
+    b32 = None if bias is None else bias.detach().float().contiguous()
+    y = torch.empty(B, OH, OW, cout, dtype=torch.float32 if out_f32 else act_dtype(), device=x.device)
+    _count_flops("conv4x4", 2.0 * B * OH * OW * 16 * cin * cout)
+    check(_lib.lib().glare_conv4x4_forward_bf16(ptr(x), int(x.dtype == torch.float32), cin, ptr(conv4x4_pack(weight)), ptr(b32), ptr(y),
+                                                int(out_f32), cout, B, H, W, cin, cout, stride, int(lrelu), stream_handle()),
+          "glare_conv4x4_forward_bf16")
+    return y
+
+
+def conv4x4_dgrad(g16, weight, in_shape, stride=2, out_f32=False):
+    """dx NHWC [B, H, W, Cin] (16-bit, or fp32 for the image-side layer) from g16 [B, OH, OW, pitch >= Cout] and the fp32 OIHW filter."""
+    require_cuda(g16, weight)
+    assert g16.dtype == act_dtype() and g16.is_contiguous()
+    B, H, W, cin = in_shape
+    cout = weight.shape[0]
+    assert weight.shape[1] == cin and g16.shape[:3] == (B, conv4x4_out(H, stride), conv4x4_out(W, stride)) and g16.shape[3] >= cout
+    dx = torch.empty(B, H, W, cin, dtype=torch.float32 if out_f32 else act_dtype(), device=g16.device)
+    _count_flops("conv4x4 dgrad", 2.0 * B * g16.shape[1] * g16.shape[2] * 16 * cin * cout)
+    check(_lib.lib().glare_conv4x4_dgrad_bf16(ptr(g16), g16.shape[3], ptr(conv4x4_pack(weight, dgrad=True)), ptr(dx), int(out_f32), cin, B, H, W,
+                                              cin, cout, stride, stream_handle()), "glare_conv4x4_dgrad_bf16")
+    return dx
+
+
+def conv4x4_im2col_t(x, stride, ldp=None, ones_row=-1):
+    """x NHWC (16-bit or fp32) -> colT [16 Cin (+ 1), ldp] 16-bit, row = ci * 16 + tap: the K-contiguous operand of the weight gradient."""
+    require_cuda(x)
+    assert x.dtype in (act_dtype(), torch.float32) and x.is_contiguous()
+    B, H, W, cin = x.shape
+    P = B * conv4x4_out(H, stride) * conv4x4_out(W, stride)
+    ldp = _rup(P, 64) if ldp is None else ldp
+    col = torch.empty(cin * 16 + (1 if ones_row >= 0 else 0), ldp, dtype=act_dtype(), device=x.device)
+    check(_lib.lib().glare_conv4x4_im2col_t_bf16(ptr(x), int(x.dtype == torch.float32), cin, B, H, W, cin, stride, ptr(col), ldp, ones_row,
+                                                 stream_handle()), "glare_conv4x4_im2col_t_bf16")
+    return col
+
+
+def conv4x4_weight_grad(x, g16, cout, stride):
+    """-> fp32 [cout, 16 Cin + 1]: dW in OIHW order and, last column, the bias gradient (im2col_t + split-K NT GEMM, as every strided conv)."""
+    _count_flops("conv4x4 wgrad", 2.0 * g16.shape[0] * g16.shape[1] * g16.shape[2] * 16 * x.shape[-1] * cout)
+    return conv_weight_grad(lambda ldp, ones_row: conv4x4_im2col_t(x, stride, ldp=ldp, ones_row=ones_row), g16, cout, x.shape[-1] * 16)
+
+
+def lrelu_backward(g16, y16):
+    """g * (y > 0 ? 1 : 0.2), 16-bit: LeakyReLU(0.2)'s backward behind a conv that fused it."""
+    require_cuda(g16, y16)
+    assert g16.dtype == y16.dtype == act_dtype() and g16.is_contiguous() and y16.is_contiguous() and g16.shape == y16.shape
+    out = torch.empty_like(g16)
+    check(_lib.lib().glare_lrelu_backward_bf16(ptr(g16), ptr(y16), ptr(out), g16.numel(), stream_handle()), "glare_lrelu_backward_bf16")
+    return out
+
+
+def batchnorm_forward(x, gamma, beta, groups=1, lrelu=True, eps=1e-5, momentum=0.1, running_mean=None, running_var=None,
+                      num_batches_tracked=None):
+    """Training-mode BatchNorm2d [+ LeakyReLU(0.2)] on 16-bit NHWC, statistics per run of B / groups consecutive images.
+    -> (y, saved fp32 [groups, 2, C] = (mean, rstd)); the running buffers (fp32 [C], int64 scalar) are updated in place, once per group."""
+    require_cuda(x, gamma, beta, running_mean, running_var, num_batches_tracked)
+    assert x.dtype == act_dtype() and x.is_contiguous() and x.dim() == 4
+    B, H, W, C = x.shape
+    assert B % groups == 0, "batch %d is not %d equal groups" % (B, groups)
+    g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+    for t in (running_mean, running_var):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C)
+    assert num_batches_tracked is None or (num_batches_tracked.dtype == torch.int64 and num_batches_tracked.numel() == 1)
+    lib = _lib.lib()
+    nws = lib.glare_batchnorm_workspace_bytes(B, H * W, C, groups)
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
+    y = torch.empty_like(x)
+    saved = torch.empty(groups, 2, C, dtype=torch.float32, device=x.device)
+    check(lib.glare_batchnorm_lrelu_bf16(ptr(x), ptr(g32), ptr(b32), ptr(y), B, H * W, C, groups, eps, momentum, int(lrelu), ptr(saved),
+                                         ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), ptr(ws), nws, stream_handle()),
+          "glare_batchnorm_lrelu_bf16")
+    return y, saved
+
+
+def batchnorm_backward(x, dy, saved, gamma, beta, groups=1, lrelu=True):
+    """-> (dx 16-bit, dgamma fp32 [C], dbeta fp32 [C]) through the activation; statistics per group as the forward took them."""
+    require_cuda(x, dy, saved, gamma, beta)
+    assert x.dtype == dy.dtype == act_dtype() and x.is_contiguous() and dy.is_contiguous() and x.shape == dy.shape
+    B, H, W, C = x.shape
+    assert saved.dtype == torch.float32 and saved.is_contiguous() and tuple(saved.shape) == (groups, 2, C)
+    g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+    lib = _lib.lib()
+    nws = lib.glare_batchnorm_workspace_bytes(B, H * W, C, groups)
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
+    dx = torch.empty_like(x)
+    dgamma, dbeta = (torch.empty(C, dtype=torch.float32, device=x.device) for _ in range(2))
+    check(lib.glare_batchnorm_lrelu_backward_bf16(ptr(x), ptr(dy), ptr(saved), ptr(g32), ptr(b32), ptr(dx), ptr(dgamma), ptr(dbeta), B, H * W, C,
+                                                  groups, int(lrelu), ptr(ws), nws, stream_handle()), "glare_batchnorm_lrelu_backward_bf16")
+    return dx, dgamma, dbeta
+
+
+HINGE_MODES = {"real": 0, "fake": 1, "generator": 2}
+
+
+def hinge_loss(x, mode, want_grad=True):
+    """fp32 logits (any shape) -> (loss fp32 [1], d loss / d x like x or None).  mode "real": mean relu(1 - x); "fake": mean relu(1 + x);
+    "generator": -mean x.  Fixed two-level sum."""
+    require_cuda(x)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0
+    lib = _lib.lib()
+    nws = lib.glare_hinge_workspace_bytes(x.numel())
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    grad = torch.empty_like(x) if want_grad else None
+    check(lib.glare_hinge_loss_f32(ptr(x), x.numel(), HINGE_MODES[mode], ptr(loss), ptr(grad), ptr(ws), nws, stream_handle()),
+          "glare_hinge_loss_f32")
+    return loss, grad

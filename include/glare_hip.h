@@ -864,6 +864,46 @@ size_t glare_lpips_tap_workspace_bytes(int B, long long HW);
 int glare_lpips_tap_f32(const float* feat0_nchw, const float* feat1_nchw, const float* lin_w, int B, int C, long long HW, float eps,
                         int accumulate, double* dist_out, void* workspace, size_t workspace_bytes, glare_stream_t stream);
 
+/* ---- stage 1, GAN term: the patch discriminator (taming's NLayerDiscriminator; csrc/conv4x4.hip, csrc/disc_ops.hip) ----------------
+ * 4x4 convolution, zero padding 1, stride 1 or 2 (OH = (H - 2) / stride + 1), NHWC, fp32 accumulation on MFMA 16x16x32, every sum in
+ * one fixed order (bitwise reproducible, no atomics).  The filter is packed per direction from the fp32 OIHW master:
+ *   glare_conv4x4_packed_elems(Cout, Cin, dgrad) 16-bit elements; glare_conv4x4_pack_bf16 fills them (dgrad = 0: forward, 1: data gradient).
+ * glare_conv4x4_forward_bf16: y = [lrelu0.2](conv(x) + bias); x 16-bit or fp32 (x_is_f32: the reconstruction in front of layer 1), y 16-bit
+ *   or fp32; bias NULL or fp32 [Cout]; pitches in elements.  glare_conv4x4_dgrad_bf16: dx [B][H][W][dx_pitch] (16-bit or fp32) from
+ *   g 16-bit [B][OH][OW][g_pitch] (channels [Cout, g_pitch) are not read); stride 2 runs as four parity classes of four taps each.
+ * glare_conv4x4_im2col_t_bf16: colT[ci * 16 + tap][p] (p = (b, oy, ox), columns [P, ldp) zero, ldp % 64 == 0; ones_row = 16 Cin adds a
+ *   row of ones, -1 none): with glare_transpose_bf16 and glare_gemm_nt_bf16 the weight (and bias) gradient in OIHW order.
+ * Pixel counts of 2^31 and more are GLARE_ERR_UNSUPPORTED (pixel indices are 32-bit, element offsets 64-bit). */
+long long glare_conv4x4_packed_elems(int Cout, int Cin, int dgrad);
+int glare_conv4x4_pack_bf16(const float* w_oihw, int Cout, int Cin, int dgrad, void* packed, glare_stream_t stream);
+int glare_conv4x4_forward_bf16(const void* x, int x_is_f32, int x_pitch, const void* packed, const float* bias, void* y, int y_is_f32,
+                               int y_pitch, int B, int H, int W, int Cin, int Cout, int stride, int lrelu, glare_stream_t stream);
+int glare_conv4x4_dgrad_bf16(const void* g, int g_pitch, const void* packed, void* dx, int dx_is_f32, int dx_pitch, int B, int H, int W,
+                             int Cin, int Cout, int stride, glare_stream_t stream);
+int glare_conv4x4_im2col_t_bf16(const void* x, int x_is_f32, int x_pitch, int B, int H, int W, int Cin, int stride, void* colT,
+                                long long ldp, int ones_row, glare_stream_t stream);
+/* nn.BatchNorm2d in training mode [+ LeakyReLU(0.2)] on dense 16-bit NHWC [B][HW][C], statistics in fp32 (two-pass variance), per run of
+ * B / groups consecutive images ("batch groups": real and fake batches in one set of launches with the statistics of two calls).
+ *   y = lrelu(gamma (x - mean) rstd + beta);  saved_stats fp32 [groups][2][C] = (mean, rstd = 1 / sqrt(var + eps)), read by the backward.
+ *   running_mean / running_var (NULL: not tracked) take one momentum update per group in group order (running_var from the unbiased
+ *   variance), num_batches_tracked (int64, NULL: not tracked) += groups -- what `groups` separate calls of nn.BatchNorm2d leave.
+ *   backward: dx 16-bit, dgamma / dbeta fp32 [C] (summed over the groups), through the activation.
+ * workspace: glare_batchnorm_workspace_bytes bytes, caller-owned (both entries).  No atomics; every sum's order depends on the shape alone. */
+size_t glare_batchnorm_workspace_bytes(int B, long long HW, int C, int groups);
+int glare_batchnorm_lrelu_bf16(const void* x, const float* gamma, const float* beta, void* y, int B, long long HW, int C, int groups,
+                               float eps, float momentum, int lrelu, float* saved_stats, float* running_mean, float* running_var,
+                               long long* num_batches_tracked, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+int glare_batchnorm_lrelu_backward_bf16(const void* x, const void* dy, const float* saved_stats, const float* gamma, const float* beta,
+                                        void* dx, float* dgamma, float* dbeta, int B, long long HW, int C, int groups, int lrelu,
+                                        void* workspace, size_t workspace_bytes, glare_stream_t stream);
+/* out = g * (y > 0 ? 1 : 0.2): LeakyReLU(0.2)'s backward where a conv fused it (y = the conv's stored output), 16-bit, n elements. */
+int glare_lrelu_backward_bf16(const void* g, const void* y, void* out, long long n, glare_stream_t stream);
+/* Hinge / generator losses of the GAN term on fp32 logits, fixed two-level sum (as glare_vq_loss_sum_f32), n < 2^24:
+ *   mode 0: mean relu(1 - x)   mode 1: mean relu(1 + x)   mode 2: -mean x;   loss fp32 [1]; grad (NULL: none) fp32 [n] = d loss / d x. */
+size_t glare_hinge_workspace_bytes(long long n);
+int glare_hinge_loss_f32(const float* x, long long n, int mode, float* loss, float* grad, void* workspace, size_t workspace_bytes,
+                         glare_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,12 @@
 """Time stage 1 on the GPU: one fp16 Stage1Trainer step at the reference crop (4 x 3 x 256 x 256), and the codebook layer's new launches
 (csrc/vq_train.hip) alone against the same step's glare_vq_nearest_f32 launch, on the step's own token count (4 x 64 x 64) and on
 the largest the layer is specified for (8 x 16 275).  Device events around repeated launches on preallocated buffers; every shape is
-warmed up first.  `python tools/stage1_time.py [--out profiles/stage1_step.txt]`"""
+warmed up first.  `python tools/stage1_time.py [--out profiles/stage1_step.txt]`
+
+`--gan`: instead, the same step with and without the patch discriminator (disc_start = 0) in one session, and every launch the discriminator
+adds timed alone at the step's shapes (8 = 4 real + 4 fake images, two batch groups); for the four 64-to-512-channel conv layers the share of
+the dense 16-bit peak their forward, data-gradient and weight-gradient launches reach.
+`python tools/stage1_time.py --gan [--out profiles/stage1_gan_step.txt]`"""
 import argparse
 import os
 import sys
@@ -50,12 +55,87 @@ def launches(N, K, reps):
     return {"vq_nearest": timed(near, reps), "vq_loss_sum": timed(fwd, reps), "vq_backward": timed(bwd, reps), "vq_backward dz only": timed(bwd_dz, reps)}
 
 
+PEAK_TFLOPS = 2500.0      # dense bf16 / fp16 MFMA peak of one MI355X (spec)
+
+
+def gan(args):
+    """The fp16 step at 4 x 3 x 256^2 without and with the discriminator, then D's launches one by one."""
+    from glare_amd import ops
+    from glare_amd import train_ops as T
+
+    dev = torch.device("cuda", 0)
+    lines = ["stage 1 with the patch discriminator on %s (tools/stage1_time.py --gan; device events, warmed up, ms; one session)"
+             % torch.cuda.get_device_name(0)]
+    x = torch.rand(4, 3, 256, 256, generator=torch.Generator().manual_seed(0)).to(dev)
+    res = {}
+    for name in ("plain", "gan"):
+        torch.manual_seed(0)
+        disc = M.NLayerDiscriminator().to(dev) if name == "gan" else None
+        tr = Stage1Trainer(seeded_init_(M.VQModel().train(), 1).to(dev), precision="fp16", discriminator=disc, disc_start=0)
+        tr.opt.scale.fill_(1024.0)
+        if disc is not None:
+            tr.opt_d.scale.fill_(1024.0)
+        res[name] = timed(lambda: tr.step_tensor(x), args.steps, warm=3)
+        lines.append("Stage1Trainer.step_tensor fp16, 4 x 3 x 256 x 256, %-5s (eager, %d steps): %.2f ms per step, generator steps applied %d of %d%s"
+                     % (name, args.steps, res[name], tr.opt.t, args.steps + 3, "" if disc is None else ", discriminator %d" % tr.opt_d.t))
+        del tr
+    lines.append("the discriminator's share of the step: %.2f ms = %.1f %% (the parent commit measured 34.3 ms for the plain step on another day:"
+                 " quoted, not compared)" % (res["gan"] - res["plain"], 100 * (res["gan"] - res["plain"]) / res["gan"]))
+    lines.append("")
+    lines.append("the discriminator's launches alone, 8 x 3 x 256 x 256 (real + fake), fp16, %d launches each:" % args.reps)
+    lines.append("  %-34s %9s %9s %8s" % ("launch", "ms", "GFLOP", "of peak"))
+    total = 0.0
+    with ops.use_precision("fp16"), torch.no_grad():
+        g = torch.Generator().manual_seed(1)
+        layers = ((3, 64, 2, 256), (64, 128, 2, 128), (128, 256, 2, 64), (256, 512, 1, 32), (512, 1, 1, 31))
+        for i, (cin, cout, stride, side) in enumerate(layers, 1):
+            xin = torch.rand(8, side, side, cin, generator=g).to(dev)
+            if cin != 3:
+                xin = xin.to(ops.act_dtype())
+            w = (torch.randn(cout, cin, 4, 4, generator=g) * 0.02).to(dev)
+            o = T.conv4x4_out(side, stride)
+            g16 = torch.randn(8, o, o, max(cout, 8), generator=g).to(dev).to(ops.act_dtype())
+            gf = 2.0 * 8 * o * o * 16 * cin * cout / 1e9
+            rows = [("conv%d %d->%d s%d forward" % (i, cin, cout, stride), lambda: T.conv4x4_forward(xin, w, stride=stride, lrelu=i == 1, out_f32=i == 5)),
+                    ("conv%d data gradient" % i, lambda: T.conv4x4_dgrad(g16, w, (8, side, side, cin), stride=stride, out_f32=cin == 3)),
+                    ("conv%d weight gradient" % i, lambda: T.conv4x4_weight_grad(xin, g16, cout, stride))]
+            for label, fn in rows:
+                ms = timed(fn, args.reps)
+                total += ms
+                peak = "%7.2f%%" % (100 * gf / ms / PEAK_TFLOPS) if 64 <= cin and cout >= 64 else "       -"
+                lines.append("  %-34s %9.4f %9.3f %s" % (label, ms, gf, peak))
+            if 2 <= i <= 4:
+                y = torch.randn(8, o, o, cout, generator=g).to(dev).to(ops.act_dtype())
+                ga, be = torch.ones(cout, device=dev), torch.zeros(cout, device=dev)
+                _, saved = T.batchnorm_forward(y, ga, be, groups=2)
+                for label, fn in (("batchnorm%d + lrelu forward (4 launches)" % i, lambda: T.batchnorm_forward(y, ga, be, groups=2)),
+                                  ("batchnorm%d + lrelu backward (3)" % i, lambda: T.batchnorm_backward(y, y, saved, ga, be, groups=2))):
+                    ms = timed(fn, args.reps)
+                    total += ms
+                    lines.append("  %-34s %9.4f %9s %s" % (label, ms, "-", "       -"))
+        logits = torch.randn(4, 30, 30, 1, generator=g).to(dev)
+        ms = timed(lambda: T.hinge_loss(logits, "real"), args.reps)
+        total += 3 * ms
+        lines.append("  %-34s %9.4f %9s %s" % ("hinge reduction (2 launches), x 3", ms, "-", "       -"))
+    lines.append("  sum of the launches above (the weight-gradient rows include im2col_t, transpose, GEMM and the packs): %.3f ms" % total)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=None)
     ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--gan", action="store_true", help="time the step with and without the patch discriminator, and its launches alone")
+    ap.add_argument("--reps", type=int, default=50)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
+    if args.gan:
+        text = "\n".join(gan(args)) + "\n"
+        print(text, end="")
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text)
+        return
     dev = torch.device("cuda", 0)
     lines = ["stage 1 on %s (tools/stage1_time.py; device events, warmed up, ms)" % torch.cuda.get_device_name(0)]
     tr = Stage1Trainer(seeded_init_(M.VQModel().train(), 1).to(dev), precision="fp16")
