@@ -3,7 +3,9 @@ Each is written from the mathematics in the header comments of csrc/flow_bwd.hip
 its derivative), not from the kernels' loops, and test_backward_fp64_host.py checks every one against fp64 AUTOGRAD of the forward
 operation -- so that the GPU test's reference is not a copy of the code under test.  Tensors keep the kernels' layouts (channels
 last); where a kernel leaves per-block partial sums, the restatement returns the per-pixel TERMS of the sum and the test adds
-them over the pixels it expects a block to own.  A plain module like tolerances.py."""
+them over the pixels it expects a block to own.  The second half holds the references of test_gpu_matrix_backward.py: attention on
+base-2 logits and its backward (the header of csrc/attn_bwd.hip), the row softmax, the weight gradient of csrc/wgrad.hip, and the
+exact-arithmetic operands of the fused backward with their single-term condition.  A plain module like tolerances.py."""
 import torch
 import torch.nn.functional as F
 
@@ -145,3 +147,133 @@ def act_backward(g, y, act):
 def h1_forward(z0, wz):
     """z0 [B, H, W], wz [64, 9] -> [B, H, W, 64]"""
     return F.conv2d(z0.unsqueeze(1), wz.view(64, 1, 3, 3), padding=1).permute(0, 2, 3, 1)
+
+
+# ---- single-head attention on base-2 logits (csrc/attn.hip, csrc/attn_bwd.hip) -----------------------------------------------------
+def attention_fp64(q, k, v):
+    """q (scale and log2 e folded in), k, v [B, N, d] -> (O [B, N, d], L [B, N]): s_ij = q_i . k_j, L_i = log2 sum_j 2^s_ij,
+    O_i = sum_j 2^(s_ij - L_i) v_j"""
+    s = q @ k.transpose(-1, -2)
+    m = s.amax(-1, keepdim=True)
+    e = torch.exp2(s - m)
+    l = e.sum(-1, keepdim=True)
+    return (e / l) @ v, (m + torch.log2(l)).squeeze(-1)
+
+
+def attention_backward_terms(q, k, v, o, do, L, ln2_scale):
+    """-> (s, p, dp, D, ds): p = 2^(s - L), dp = do . v, D = do . o, ds = ln2_scale p (dp - D).  `o` and `L` are INPUTS, as they are
+    for the kernel (the header of csrc/attn_bwd.hip): nothing here recomputes them"""
+    s = q @ k.transpose(-1, -2)
+    p = torch.exp2(s - L.unsqueeze(-1))
+    dp = do @ v.transpose(-1, -2)
+    D = (do * o).sum(-1)
+    return s, p, dp, D, ln2_scale * p * (dp - D.unsqueeze(-1))
+
+
+def attention_backward_fp64(q, k, v, o, do, L, ln2_scale):
+    """-> (dq = ds k, dk = ds^T q, dv = p^T do, D)"""
+    _, p, _, D, ds = attention_backward_terms(q, k, v, o, do, L, ln2_scale)
+    return ds @ k, ds.transpose(-1, -2) @ q, p.transpose(-1, -2) @ do, D
+
+
+def softmax2_rows_fp64(S):
+    """P_ij = 2^S_ij / sum_j 2^S_ij"""
+    e = torch.exp2(S - S.amax(-1, keepdim=True))
+    return e / e.sum(-1, keepdim=True)
+
+
+def attention_ds_fp64(P, dP, dO, O, scale):
+    """dS_ij = scale P_ij (dP_ij - delta_i), delta_i = dO_i . O_i -> (dS, delta)"""
+    delta = (dO * O).sum(-1)
+    return scale * P * (dP - delta.unsqueeze(-1)), delta
+
+
+# ---- weight gradient of a k x k / stride-1 / pad k // 2 convolution (csrc/wgrad.hip) ------------------------------------------------
+def conv_weight_grad_fp64(x, g, ksize):
+    """x [B, H, W, Ci], g [B, H, W, Co] -> (dW [Co, Ci, k, k], db [Co]): dW[co][ci][ty][tx] = sum_{b,y,x} g[b][y][x][co]
+    x[b][y + ty - h][x + tx - h][ci] with zeros outside the image (h = k // 2), db[co] = sum g"""
+    h = ksize // 2
+    taps = [torch.einsum("byxo,byxi->oi", g, _shifted(x, ty - h, tx - h)) for ty in range(ksize) for tx in range(ksize)]
+    return torch.stack(taps, -1).view(g.shape[-1], x.shape[-1], ksize, ksize), g.sum((0, 1, 2))
+
+
+# ---- exact-arithmetic operands of the fused attention backward (test_gpu_matrix_backward.py, section 5) ---------------------------
+EXACT_CH = (0, 300)          # the two score channels, one in each 256-channel half
+# (B, N) of the fused backward's per-element tests: one token; 1 / 1 / 2 streamed tiles of 32 with the 64-row resident block mostly empty;
+# the resident block boundary and an image offset with a ragged tail; 4 tiles, 2 blocks; 5 tiles (odd) and 9 workgroups (XCD remap
+# remainder 1); 12 workgroups (remainder 4); the size of test_gpu_train.py
+ATTN_CASES = ((1, 1), (1, 31), (1, 32), (1, 33), (2, 63), (1, 64), (2, 65), (1, 97), (3, 129), (3, 200), (1, 330))
+EXACT_CASES = ATTN_CASES + ((2, 1000),)          # 32 tiles, the split-key forward's size
+EXACT_CASE_LARGE = (1, 105 * 155)                # one 400 x 600 image's latent, 16 275 tokens: run on the GPU only (2.6e8 scores)
+FORMATS = {"bf16": (7, -126), "fp16": (10, -14)}          # mantissa bits, smallest normal exponent
+
+
+def exact_attention_case(B, N):
+    """Operands with which every product, partial sum, p and ds of the fused backward is exact in fp32 and in either 16-bit format,
+    so that the ONLY rounding left is the output's.  All fp64, integer valued:
+        q_i = a_i e_0 + a'_i e_300, k_j = b_j e_0 + b'_j e_300      s_ij = a_i b_j + a'_i b'_j, an integer
+        L_i = max_j possible s_ij + off_i                           p_ij = 2^(s_ij - L_i), a power of two in [2^-6, 1]
+        do_i: two non-zeros in {+-1, +-2, +-3} at channels c_i = (7 i + 3) mod 512 and c_i + 256: one in each half, and for N <= 256 no two
+              rows share a channel;  v, o: integers in [-3, 3] and [-2, 2] that depend on (row, channel) -- dp_ij and D_i are two-term sums
+    Rows are distinguishable: a, a', off, the positions and values of do, and v / o change with the row (rows i and i + 8, which a lane
+    shuffle could confuse, differ in L); every image differs (the row index runs on across the batch).  N <= 256 uses the whole range
+    of p; above it several rows share a channel of dv, and the range is [2^-2, 1] with |do| <= 2 so that one term stays visible next
+    to the others in 8 significant bits (single_term_sensitivity asserts it)."""
+    wide = N <= 256
+    r = (torch.arange(B * N).view(B, N) + 5 * torch.arange(B).view(B, 1)).double()          # the row index, running on across the batch
+    c = torch.arange(512).double()
+    if wide:
+        a, a2, off = 1 + r % 2, 1 - 2 * ((r // 2) % 2), (r // 8) % 2
+        b, b2 = r % 3, (r // 3) % 2
+        Lmax = 2 * a + a2.clamp_min(0)                                                      # b <= 2, b' <= 1
+    else:
+        a, a2, off = 1 - 2 * (r % 2), 1 - 2 * ((r // 8) % 2), torch.zeros_like(r)
+        b, b2 = r % 2, (r // 2) % 2
+        Lmax = a.clamp_min(0) + a2.clamp_min(0)
+    q, k = torch.zeros(B, N, 512, dtype=torch.float64), torch.zeros(B, N, 512, dtype=torch.float64)
+    q[..., EXACT_CH[0]], q[..., EXACT_CH[1]] = a, a2
+    k[..., EXACT_CH[0]], k[..., EXACT_CH[1]] = b, b2
+    L = Lmax + off
+    do = torch.zeros(B, N, 512, dtype=torch.float64)
+    ch = ((7 * r + 3) % 512).long()
+    top = 3 if wide else 2
+    val1 = (1 + r % top) * (1 - 2 * ((r // 3) % 2))
+    val2 = (1 + (r // 2) % top) * (1 - 2 * ((r // 5) % 2))
+    do.scatter_(2, ch.unsqueeze(-1), val1.unsqueeze(-1))
+    do.scatter_(2, ((ch + 256) % 512).unsqueeze(-1), val2.unsqueeze(-1))
+    rr = r.unsqueeze(-1)
+    v = (rr * (2 * c + 1) + c) % 7 - 3
+    o = (rr + 3 * c) % 5 - 2
+    return q, k, v, o, do, L
+
+
+def _ulp(v, m, emin):
+    """the spacing of the 16-bit format (m mantissa bits, smallest normal exponent emin) at |v|"""
+    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** emin)))
+    e = torch.where(torch.exp2(e) > v.abs().clamp_min(2.0 ** emin), e - 1, e)
+    return torch.exp2(e.clamp_min(emin) - m)
+
+
+def exact_attention_bounds(q, k, v, o, do, L, m, emin, n_u=3.0):
+    """-> (dq, dk, dv exact), (their bounds 0.5 ulp16(exact) + n_u U sum |terms|), (p, ds)"""
+    U = 2.0 ** -24
+    _, p, _, _, ds = attention_backward_terms(q, k, v, o, do, L, 1.0)
+    exact = (ds @ k, ds.transpose(-1, -2) @ q, p.transpose(-1, -2) @ do)
+    mags = (ds.abs() @ k.abs(), ds.abs().transpose(-1, -2) @ q.abs(), p.transpose(-1, -2) @ do.abs())
+    return exact, tuple(0.5 * _ulp(e, m, emin) + n_u * U * g for e, g in zip(exact, mags)), (p, ds)
+
+
+def single_term_sensitivity(q, k, do, p, ds, bounds):
+    """[B, N, N]: for every (i, j), the largest |change| / bound over the output elements that the term (i, j) feeds when it alone is
+    removed from the sums: dv_j[c] loses p_ij do_i[c], dk_j[c] loses ds_ij q_i[c], dq_i[c] loses ds_ij k_j[c]"""
+    bq, bk, bv = bounds
+    best = torch.zeros_like(p)
+    for c in EXACT_CH:                                                        # q and k are zero elsewhere
+        best = torch.maximum(best, ds.abs() * q[..., c].abs().unsqueeze(-1) / bk[..., c].unsqueeze(-2))
+        best = torch.maximum(best, ds.abs() * k[..., c].abs().unsqueeze(-2) / bq[..., c].unsqueeze(-1))
+    assert int((do != 0).sum(-1).max()) <= 2
+    val, idx = do.abs().topk(2, dim=-1)                                       # the two non-zeros of row i: dv_j[idx] is what it feeds
+    img = torch.arange(do.shape[0], device=do.device).view(-1, 1)
+    for t in range(2):
+        best = torch.maximum(best, p * val[..., t:t + 1] / bv.transpose(1, 2)[img, idx[..., t]])
+    return best

@@ -148,3 +148,74 @@ def test_act_backward(act):
     y = torch.relu(x) if act == "relu" else torch.sigmoid(x)
     ax, = torch.autograd.grad((y * gout).sum(), (x,))
     _close(R.act_backward(gout, y.detach(), act), ax, act)
+
+
+# ---- attention, the row softmax, the weight gradient (references of test_gpu_matrix_backward.py) ---------------------------------
+@pytest.mark.parametrize("N", (1, 33, 65))
+def test_attention_forward_and_backward(N):
+    g = torch.Generator().manual_seed(40 + N)
+    B, d = 2, 512
+    q, k, v = _leaf(_rand(g, B, N, d) * 0.2), _leaf(_rand(g, B, N, d)), _leaf(_rand(g, B, N, d))
+    do = _rand(g, B, N, d)
+    s = q @ k.transpose(1, 2)
+    out = torch.softmax(s * math.log(2.0), -1) @ v
+    aq, ak, av = torch.autograd.grad((out * do).sum(), (q, k, v))
+    O, L = R.attention_fp64(q.detach(), k.detach(), v.detach())
+    _close(O, out.detach(), "O")
+    _close(L, torch.logsumexp(s.detach() * math.log(2.0), -1) / math.log(2.0), "L")
+    dq, dk, dv, D = R.attention_backward_fp64(q.detach(), k.detach(), v.detach(), O, do, L, math.log(2.0))
+    if N == 1:          # one key: p = 1 whatever q and k are, both gradients vanish (dp = D up to the rounding of O)
+        assert float(aq.abs().max()) == 0 and float(ak.abs().max()) == 0 and float(dq.abs().max()) < REL and float(dk.abs().max()) < REL
+    else:
+        _close(dq, aq, "dq")
+        _close(dk, ak, "dk")
+    _close(dv, av, "dv")
+    _close(D, (do * out.detach()).sum(-1), "D")
+
+
+def test_softmax2_rows_and_attention_ds():
+    g = torch.Generator().manual_seed(44)
+    n, d = 37, 24
+    S, v = _leaf(_rand(g, 3, n) * 4), _rand(g, n, d)
+    dO = _rand(g, 3, d)
+    P = torch.softmax(S * math.log(2.0), -1)
+    O = P @ v
+    aS, = torch.autograd.grad((O * dO).sum(), (S,))
+    P64 = R.softmax2_rows_fp64(S.detach())
+    _close(P64, P.detach(), "P")
+    dS, delta = R.attention_ds_fp64(P64, dO @ v.t(), dO, O.detach(), math.log(2.0))
+    _close(dS, aS, "dS")
+    _close(delta, (dO * O.detach()).sum(-1), "delta")
+
+
+@pytest.mark.parametrize("ksize", (1, 3))
+@pytest.mark.parametrize("B,H,W,Ci,Co", ((1, 1, 1, 8, 8), (1, 1, 17, 8, 16), (2, 3, 15, 16, 8), (2, 5, 7, 8, 24)))
+def test_conv_weight_grad(B, H, W, Ci, Co, ksize):
+    g = torch.Generator().manual_seed(H * 16 + W + ksize)
+    x, gy = _rand(g, B, H, W, Ci), _rand(g, B, H, W, Co)
+    dW, db = R.conv_weight_grad_fp64(x, gy, ksize)
+    ref = torch.nn.grad.conv2d_weight(x.permute(0, 3, 1, 2), (Co, Ci, ksize, ksize), gy.permute(0, 3, 1, 2), padding=ksize // 2)
+    _close(dW, ref, "dW")
+    _close(db, gy.sum((0, 1, 2)), "db")
+
+
+@pytest.mark.parametrize("fmt", sorted(R.FORMATS))
+@pytest.mark.parametrize("B,N", R.EXACT_CASES)
+def test_exact_attention_operands_are_exact_and_show_every_single_term(B, N, fmt):
+    """The preconditions of the exact-arithmetic family: integer operands, p a power of two in [2^-6, 1], ds representable in the format's
+    significand, every partial sum an exact fp32 number; and removing ANY single (i, j) term from the reference moves at least one
+    output element by more than twice its bound.  (EXACT_CASE_LARGE meets all of it as well -- smallest ratio 16.0 in bf16, 127.8 in
+    fp16 -- but takes half a minute per format on a CPU: test_gpu_matrix_backward.py asserts the same on the device.)"""
+    m, emin = R.FORMATS[fmt]
+    q, k, v, o, do, L = R.exact_attention_case(B, N)
+    for t in (q, k, v, o, do, L):
+        assert torch.equal(t, t.round()) and float(t.abs().max()) <= (6 if t is L else 3)
+    exact, bounds, (p, ds) = R.exact_attention_bounds(q, k, v, o, do, L, m, emin)
+    e = torch.log2(p)
+    assert torch.equal(e, e.round()) and float(e.min()) >= -6 and float(e.max()) <= 0
+    assert N == 1 or float(e.min()) < float(e.max())
+    assert float((ds / p).abs().max()) < 2 ** (m + 1) and torch.equal(ds / p, (ds / p).round())          # ds = p * an integer of <= m + 1 bits
+    for mag in (ds.abs() @ k.abs(), ds.abs().transpose(1, 2) @ q.abs(), p.transpose(1, 2) @ do.abs()):
+        assert float(mag.max()) / float(p.min()) < 2 ** 24                                                # multiples of the smallest p: exact in fp32
+    sens = R.single_term_sensitivity(q, k, do, p, ds, bounds)
+    assert float(sens.min()) > 2.0, float(sens.min())
