@@ -664,3 +664,49 @@ class HingeLossFn(torch.autograd.Function):
 
 def hinge_loss(x, mode):
     return HingeLossFn.apply(x, mode)
+
+
+@_lib.keeps_precision
+class LpipsHeadFn(torch.autograd.Function):
+    """One LPIPS tap on 16-bit NHWC feature maps -> fp32 [B] (train_ops.lpips_head); only `a` is differentiated.  The gradient is formed in
+    fp32 in backward, where the upstream g (with the loss weight, 1 / B and the GradScaler's scale under fp16) is known, and rounded to
+    16 bits once, as MseFn does and for its reason: unscaled, the 1 / HW factor produces fp16 subnormals.  The backward recomputes the norms
+    from a and b; a pixel of `a` that is all zero gets gradient 0 (autograd: NaN)."""
+
+    @staticmethod
+    def forward(ctx, a, b, w):
+        a, b, w = a.contiguous(), b.contiguous(), w.detach().float().reshape(-1).contiguous()
+        out = T.lpips_head(a, b, w)
+        if ctx.needs_input_grad[0]:        # only then is there a backward that reads them (the `x` side runs under no_grad)
+            ctx.save_for_backward(a, b, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        a, b, w = ctx.saved_tensors
+        return T.lpips_head_backward(a, b, w, g.detach().float().contiguous()), None, None
+
+
+def lpips_head(a, b, w):
+    return LpipsHeadFn.apply(a, b, w)
+
+
+@_lib.keeps_precision
+class ImageAffineFn(torch.autograd.Function):
+    """x * mul[c] + add[c] on an fp32 NHWC image (LPIPS' ScalingLayer on 2 x - 1 as one map); backward: the same kernel with mul alone."""
+
+    @staticmethod
+    def forward(ctx, x, mul, add):
+        ctx.save_for_backward(mul)
+        return T.image_affine(x.contiguous(), mul, add)
+
+    @staticmethod
+    def backward(ctx, g):
+        (mul,) = ctx.saved_tensors
+        return T.image_affine(g.contiguous().float(), mul), None, None
+
+
+def image_affine(x, mul, add):
+    return ImageAffineFn.apply(x, mul, add)

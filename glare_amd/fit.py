@@ -5,9 +5,15 @@ code/train_stage3.py:138-300 over models/base_model.py:46-83 and models/lr_sched
     python -m glare_amd.fit stage1 --root LOLdataset --out prior [--net-vq start.pth]
     python -m glare_amd.fit stage3 --root LOLdataset --out run --net-g stage2_G.pth --net-vq vqgan.pkl
     python -m glare_amd.fit stage3 --root LOLdataset --out run --resume run/training_state/500.state
+    python -m glare_amd.fit stage1 --root LOLdataset --out prior --vgg16 vgg16.pth --lpips-heads vgg.pth [--gan]
+    python -m glare_amd.fit stage3 --root LOLdataset --out run --net-g stage2_G.pth --net-vq vqgan.pkl --vgg16 vgg16.pth
 
 Stage 1 trains the VQGAN prior itself (VQModel_arch.py:98-101, 148-157) on the ground-truth half of the pairs and writes
 <out>/models/<iter>_VQ.pth under the reference's VQModel key names: what `--net-vq` of stages 2 and 3, `evaluate` and `enhance` load.
+--vgg16 / --lpips-heads add the perceptual terms of the reference's objectives from the user's weight files (stage 1: LPIPS on VGG16, both
+files; stage 3: the VGG16-feature loss, --vgg16 alone; losses.load_vgg16 refuses a file that lacks a tensor).  The loss networks are frozen and
+are written to no checkpoint: a resumed run names the same files again (the .state records that the run had the term, and a resume
+without it, or with another --perceptual-weight, is refused).
 The reference ships no stage-1 configuration (its prior is a download): `lr_G` 1e-4 is a starting point, not a tuned value.
 
 What is mirrored: the option keys and their per-stage values, the seeding, the index order of the reference's DataLoader, the
@@ -213,8 +219,12 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
     set_random_seed(tr["manual_seed"])
     epoch, step, order, done = 0, 0, None, 0
     gan = getattr(trainer, "discriminator", None) is not None      # stage 1 with --gan: D's weights, optimizer and scaler travel too
+    percep = getattr(trainer, "perceptual", None)                  # the loss network travels in no file; which one it was does
+    percep = None if percep is None else "%s x %g" % (type(percep).__name__, getattr(trainer, "perceptual_weight", 1.0))
     if resume:
         st = torch.load(resume, map_location="cpu", weights_only=False) if isinstance(resume, str) else resume
+        if STATE_KEY in st and st[STATE_KEY].get("perceptual") != percep:
+            raise ValueError(PERCEPTUAL_RESUME_REFUSAL % (st[STATE_KEY].get("perceptual") or "no perceptual term", percep or "none"))
         epoch, step = checkpoint.resume_training(st, trainer, [sched])
         sched.adopt_loaded()
         if STATE_KEY in st:                  # written by this driver: continue the exact index / augmentation sequence
@@ -232,6 +242,8 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
     def save(epoch, step, order, done):
         checkpoint.save_network(trainer.netG, os.path.join(out_dir, "models", "%d_%s.pth" % (step, tag)))
         extra = {STATE_KEY: {"rng": _rng_state(), "epoch_order": order, "batches_done": done}}
+        if percep:   # (a run without the term writes the state it always wrote)
+            extra[STATE_KEY]["perceptual"] = percep
         if gan:      # <iter>_D.pth: taming's NLayerDiscriminator state dict; its Adam and GradScaler state as one more key of the .state file
             checkpoint.save_network(trainer.discriminator, os.path.join(out_dir, "models", "%d_D.pth" % step))
             extra[DISC_KEY] = {"optimizer": checkpoint.adam_state_dict(trainer.opt_d), "scaler": trainer.opt_d.scaler_state_dict()}
@@ -265,6 +277,8 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
                        "ms_batch": 1e3 * t_batch / n_win}
                 if gan:
                     rec.update((k, float(trainer.last_terms[k])) for k in GAN_TERMS)
+                if getattr(trainer, "perceptual", None) is not None:
+                    rec["percep_loss"] = float(trainer.last_terms["percep_loss"])
             if step - first == STEADY_FROM:
                 _sync()
                 t_steady = time.perf_counter()
@@ -290,14 +304,48 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
 
 
 # ---- the command ---------------------------------------------------------------------------------------------------------------
-def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16", gan=False, net_d=None):
+def check_perceptual_options(stage, vgg16=None, lpips_heads=None, perceptual_weight=None):
+    """The refusals of --vgg16 / --lpips-heads / --perceptual-weight: ValueError with the reason, before anything is built."""
+    if stage == "stage2" and (vgg16 or lpips_heads or perceptual_weight is not None):
+        raise ValueError(PERCEPTUAL_STAGE2_REFUSAL)
+    if stage == "stage3" and (lpips_heads or perceptual_weight is not None):
+        raise ValueError(PERCEPTUAL_STAGE3_REFUSAL)
+    if stage == "stage1" and bool(vgg16) != bool(lpips_heads):
+        raise ValueError(LPIPS_REFUSAL)
+    if stage == "stage1" and perceptual_weight is not None and not vgg16:
+        raise ValueError("--perceptual-weight needs --vgg16 and --lpips-heads: without them stage1 has no perceptual term to weigh")
+
+
+def build_perceptual(stage, device, vgg16=None, lpips_heads=None):
+    """The frozen loss network of the stage from the user's files (losses.load_vgg16, strict; `.loaded_keys`: what it loaded), or None
+    without --vgg16."""
+    from . import losses
+
+    if not vgg16:
+        return None
+    net = losses.LPIPSLoss() if stage == "stage1" else losses.PerceptualNetwork()
+    net.loaded_keys = losses.load_vgg16(net, vgg16, lpips_heads)
+    return net.to(device).eval()
+
+
+def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16", gan=False, net_d=None, vgg16=None,
+                  lpips_heads=None, perceptual_weight=None):
     """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer.  gan (stage 1 only): with the
-    patch discriminator (taming's initialisation under the run's seed, or the `_D.pth` file net_d)."""
+    patch discriminator (taming's initialisation under the run's seed, or the `_D.pth` file net_d).  vgg16 / lpips_heads: the weight
+    files of the perceptual term (stage 1: LPIPS, both files; stage 3: the VGG16-feature loss, the backbone alone); perceptual_weight:
+    stage 1's factor on it (default 1.0).  The loss network is frozen and is written to no checkpoint: a resumed run names the files again."""
     from . import modules as M
     from .synthetic import seeded_init_
     from .train import Stage1Trainer, Stage2Trainer, Stage3Trainer
 
+    check_perceptual_options(stage, vgg16, lpips_heads, perceptual_weight)
     tr = options["train"]
+    perceptual = build_perceptual(stage, device, vgg16, lpips_heads)
+    extra = {}
+    if perceptual is not None:         # (without the options the trainers are built exactly as before)
+        extra = dict(perceptual=perceptual)
+        if stage == "stage1":
+            extra["perceptual_weight"] = 1.0 if perceptual_weight is None else float(perceptual_weight)
     if stage == "stage1":
         if graph:
             raise ValueError(GRAPH_REFUSAL)
@@ -314,7 +362,7 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
         return Stage1Trainer(net.to(device), lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0),
                              codebook_weight=tr.get("codebook_weight", 1.0), precision=precision, discriminator=disc,
                              disc_start=tr.get("disc_start", 10000), disc_weight=tr.get("disc_weight", 0.8),
-                             disc_factor=tr.get("disc_factor", 1.0))
+                             disc_factor=tr.get("disc_factor", 1.0), **extra)
     if gan:
         raise ValueError(GAN_REFUSAL)
     net_hq = seeded_init_(M.VQModel().eval(), 1)
@@ -330,10 +378,18 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
     if stage == "stage2":
         return Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
                              train_rrdb=bool(options["network_G"].get("train_RRDB", False)), device_state=graph, precision=precision)
-    return Stage3Trainer(netG, net_hq, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0), device_state=graph, precision=precision)
+    return Stage3Trainer(netG, net_hq, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0), device_state=graph, precision=precision,
+                         **extra)
 
 
 GAN_REFUSAL = "--gan is a stage1 option: the patch discriminator belongs to the VQGAN prior's objective (stages 2 and 3 train no GAN term)"
+LPIPS_REFUSAL = ("stage1's perceptual term is LPIPS and needs both files: --vgg16 (the VGG16 backbone) and --lpips-heads (the five linear "
+                 "heads, taming's / the lpips package's vgg.pth); one without the other would leave half the network at its initialisation")
+PERCEPTUAL_STAGE3_REFUSAL = ("--lpips-heads / --perceptual-weight are stage1 options: stage3's perceptual term is the VGG16-feature MSE with its "
+                             "fixed factor 0.01 (VQLLFLOWD_model.py:217-223) and takes --vgg16 alone")
+PERCEPTUAL_RESUME_REFUSAL = ("the .state file was written by a run with %s and this one has %s: the objective would change partway through "
+                             "the run; name the same --vgg16 / --lpips-heads / --perceptual-weight again (the loss network is in no checkpoint)")
+PERCEPTUAL_STAGE2_REFUSAL = "--vgg16 / --lpips-heads / --perceptual-weight are stage1 / stage3 options: stage2's objective is the flow's NLL alone"
 GRAPH_REFUSAL = "--graph is not available for stage1: its step is not captured into a hipGraph (GraphedStep covers stages 2 and 3)"
 
 
@@ -432,6 +488,10 @@ def parse_args(argv=None):
     ap.add_argument("--gan", action="store_true", help="stage1: add the patch discriminator (hinge loss, adaptive weight); writes <iter>_D.pth")
     ap.add_argument("--disc-start", type=int, default=None, help="--gan: first step whose loss has the GAN term (default 10000)")
     ap.add_argument("--disc-weight", type=float, default=None, help="--gan: factor on the adaptive weight (default 0.8)")
+    ap.add_argument("--vgg16", default=None, help="VGG16 weights (torchvision's vgg16 state dict; also PerceptualNetwork's or LPIPS's key form): "
+                                                  "stage1 with --lpips-heads: the LPIPS term; stage3: the VGG16-feature perceptual term")
+    ap.add_argument("--lpips-heads", default=None, help="stage1: the LPIPS linear heads (taming's / the lpips package's vgg.pth)")
+    ap.add_argument("--perceptual-weight", type=float, default=None, help="stage1: factor on the LPIPS term (default 1.0)")
     ap.add_argument("--no-val", action="store_true", help="skip the closing validation")
     args = ap.parse_args(argv)
     if args.graph and args.stage == "stage1":
@@ -440,6 +500,10 @@ def parse_args(argv=None):
         ap.error(GAN_REFUSAL)
     if not args.gan and (args.disc_start is not None or args.disc_weight is not None):
         ap.error("--disc-start / --disc-weight need --gan")
+    try:
+        check_perceptual_options(args.stage, args.vgg16, args.lpips_heads, args.perceptual_weight)
+    except ValueError as e:
+        ap.error(str(e))
 
     options = default_options(args.stage)
     if args.opt:
@@ -473,7 +537,11 @@ def main(argv=None):
     train_opt = dict(options["datasets"]["train"], root=args.root)
     host_ds = D.LAYOUTS[args.layout](train_opt, train=True, all_opt=options)
     dataset = D.DeviceLoLDataset(host_ds, device)
-    trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision, gan=args.gan, net_d=net_d)
+    trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision, gan=args.gan, net_d=net_d,
+                            vgg16=args.vgg16, lpips_heads=args.lpips_heads, perceptual_weight=args.perceptual_weight)
+    if args.vgg16:        # the opening line of a run with a perceptual term: which files it was built from
+        print(json.dumps({"perceptual": type(trainer.perceptual).__name__, "vgg16": args.vgg16, "lpips_heads": args.lpips_heads,
+                          "tensors_loaded": len(trainer.perceptual.loaded_keys)}), flush=True)
     step_fn, batch_fn = graphed_fns(trainer, dataset) if args.graph else (None, None)
     validate_fn = None
     # stage 3 scores the inference path, stage 1 the prior's own reconstruction of the ground truth; stage 2 has nothing to score

@@ -9,11 +9,14 @@ torch ops on 5-element tensors.
 from math import exp
 
 import functools
+import os
+import re
 
 import torch
 import torch.nn as nn
 
 from . import autograd as A
+from . import ops
 from .modules._base import HipModule
 
 MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # pytorch_msssim/__init__.py:73
@@ -90,3 +93,158 @@ class PerceptualNetwork(HipModule):
             f_gt = self.output_features(gt)
         losses = [A.mse_loss(a, b) for a, b in zip(f_sr, f_gt)]
         return sum(losses) / len(losses)
+
+
+# torchvision's vgg16 cfg 'D': the conv indices of `features` per LPIPS slice (taps after relu1_2, relu2_2, relu3_3, relu4_3, relu5_3)
+LPIPS_SLICES = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))
+LPIPS_CHANNELS = (64, 128, 256, 512, 512)
+LPIPS_SHIFT = (-.030, -.088, -.188)      # ScalingLayer (lpips / taming): applied to 2 x - 1
+LPIPS_SCALE = (.458, .448, .450)
+
+
+class _ScalingLayer(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.register_buffer("shift", torch.tensor(LPIPS_SHIFT)[None, :, None, None])
+        self.register_buffer("scale", torch.tensor(LPIPS_SCALE)[None, :, None, None])
+
+
+class _NetLinLayer(nn.Module):
+    """`lin`: a 1x1 conv without bias behind a Dropout (the identity in eval mode)."""
+
+    def __init__(self, chn):
+        super().__init__()
+        self.model = nn.Sequential(nn.Dropout(), nn.Conv2d(chn, 1, 1, stride=1, padding=0, bias=False))
+
+
+class LPIPSLoss(HipModule):
+    """LPIPS (Zhang et al. 2018) on VGG16, the perceptual part of taming's VQLPIPSWithDiscriminator that VQModel.training_step calls as
+    `self.loss` (VQModel_arch.py:110-160), differentiable for the reconstruction: the scaling layer, vgg16.features down to relu5_3 on
+    the taped HIP convs as PerceptualNetwork runs them, and per tap the LPIPS head (autograd.lpips_head, csrc/lpips_ops.hip) on the
+    16-bit NHWC feature maps.  Module layout and parameter names are taming's / the lpips package's (`scaling_layer.shift|scale`,
+    `net.slice<k>.<torchvision index>.weight|bias`, `lin<k>.model.1.weight`), so the published files load unchanged (load_vgg16).
+    Every parameter is frozen and the module stays in eval mode.  One deviation from autograd of the published forward: a pixel of a
+    reconstruction-side feature map that is all zero gets gradient 0 from the head (autograd: NaN)."""
+
+    def __init__(self):
+        super().__init__()
+        self.scaling_layer = _ScalingLayer()
+        self.net = nn.Module()
+        cin, nxt = 3, 0
+        for k, (idx, cout) in enumerate(zip(LPIPS_SLICES, LPIPS_CHANNELS)):
+            sl = nn.Sequential()
+            if k:
+                sl.add_module(str(nxt), nn.MaxPool2d(kernel_size=2, stride=2))
+            for i in idx:
+                sl.add_module(str(i), nn.Conv2d(cin, cout, 3, padding=1))
+                sl.add_module(str(i + 1), nn.ReLU(inplace=True))
+                cin = cout
+            nxt = idx[-1] + 2
+            setattr(self.net, "slice%d" % (k + 1), sl)
+            setattr(self, "lin%d" % k, _NetLinLayer(cout))
+        for p in self.parameters():
+            p.requires_grad = False
+        super().train(False)
+
+    def train(self, mode=True):
+        return super().train(False)       # a frozen loss network: eval mode whatever the caller's .train() says
+
+    def _frozen_packs(self):
+        """The trunk's filters are packed ONCE per precision and direction (ops.FrozenPacks), not once per step."""
+        cache = self.__dict__.setdefault("_hip_cache", {})
+        if "frozen" not in cache:
+            cache["frozen"] = ops.FrozenPacks(list(self.net.parameters()))
+        return cache["frozen"]
+
+    def _affine(self):
+        def build():      # (y - shift) / scale on y = 2 x - 1 as x * mul + add, the two vectors formed in fp64
+            shift, scale = self.scaling_layer.shift.detach().double().reshape(-1), self.scaling_layer.scale.detach().double().reshape(-1)
+            return (2.0 / scale).float().contiguous(), ((-1.0 - shift) / scale).float().contiguous()
+        return self._packed("affine", build)
+
+    def _head(self, k):
+        return self._packed(("lin", k), lambda: getattr(self, "lin%d" % k).model[1].weight.detach().float().reshape(-1).contiguous())
+
+    def output_features(self, img):
+        """img: NHWC fp32 in [0, 1] -> the five taps as 16-bit NHWC."""
+        mul, add = self._affine()
+        h, feats = A.image_affine(img, mul, add), []
+        for k in range(5):
+            for m in getattr(self.net, "slice%d" % (k + 1)):
+                if isinstance(m, nn.Conv2d):                              # conv + the ReLU that follows it, fused
+                    if m.in_channels == 3:
+                        h = A.conv2d_small(h, m.weight, m.bias, layout="nhwc", act="relu")
+                    else:
+                        h = A.conv2d(h, m.weight, m.bias, act="relu")
+                elif isinstance(m, nn.MaxPool2d):
+                    h = A.maxpool2(h)
+            feats.append(h)
+        return feats
+
+    def forward(self, xrec, x):
+        """xrec, x: NHWC fp32 in [0, 1]; only xrec is differentiated.  Returns the batch mean of the per-image sum of the five taps:
+        `mean(p_loss)` of taming's nll_loss (the caller multiplies by perceptual_weight)."""
+        self._frozen_packs()
+        fa = self.output_features(xrec)
+        with torch.no_grad():
+            fb = self.output_features(x)
+        total = None
+        for k, (a, b) in enumerate(zip(fa, fb)):
+            v = A.lpips_head(a, b, self._head(k))
+            total = v if total is None else total + v
+        return total.mean()
+
+
+_BACKBONE_KEY = re.compile(r"^(?:features|vgg_model|net\.slice[1-5])\.(\d+)\.(weight|bias)$")
+
+
+def _state_dict_of(file):
+    sd = torch.load(file, map_location="cpu", weights_only=True) if isinstance(file, (str, bytes, os.PathLike)) else file
+    if not isinstance(sd, dict) or not all(torch.is_tensor(v) for v in sd.values()):
+        raise ValueError("%r does not hold a plain state dict of tensors" % (file,))
+    return sd
+
+
+def load_vgg16(module, vgg16_file, heads_file=None):
+    """The one strict loader of the VGG16 loss networks: fills a PerceptualNetwork or an LPIPSLoss from files (paths, or state dicts).
+    vgg16_file: the backbone under torchvision's keys (`features.N.*`), PerceptualNetwork's (`vgg_model.N.*`) or LPIPS's
+    (`net.sliceK.N.*`); keys the target has no use for (the classifier, deeper convs) are ignored.  heads_file: taming's / the lpips
+    package's `vgg.pth` (`linK.model.1.weight`), needed by an LPIPSLoss and refused by a PerceptualNetwork.  Every backbone and head
+    tensor of the target must be found with its shape, else ValueError names the missing / mismatched keys: nothing is left at its
+    initialisation silently.  Returns the list of the target's keys that were loaded."""
+    if vgg16_file is None:
+        raise ValueError("load_vgg16: the VGG16 backbone file is required (a heads file alone loads nothing the heads could read)")
+    want_heads = [n for n, _ in module.named_parameters() if n.startswith("lin")]
+    if heads_file is not None and not want_heads:
+        raise ValueError("load_vgg16: %s has no LPIPS heads; a heads file makes no sense for it" % type(module).__name__)
+    src = {}
+    for key, v in _state_dict_of(vgg16_file).items():
+        m = _BACKBONE_KEY.match(key)
+        if m:
+            src[(int(m.group(1)), m.group(2))] = (key, v)
+    heads = _state_dict_of(heads_file) if heads_file is not None else {}
+    targets = dict(module.named_parameters())
+    plan, missing, wrong = [], [], []
+    for name, p in targets.items():
+        m = _BACKBONE_KEY.match(name)
+        if m:
+            hit = src.get((int(m.group(1)), m.group(2)))
+            found = None if hit is None else hit[1]
+            shown = "features.%s.%s (as %s)" % (m.group(1), m.group(2), name)
+        else:
+            found = heads.get(name)
+            shown = name
+        if found is None:
+            missing.append(shown)
+        elif tuple(found.shape) != tuple(p.shape):
+            wrong.append("%s: %s in the file, %s expected" % (shown, tuple(found.shape), tuple(p.shape)))
+        else:
+            plan.append((name, p, found))
+    if missing or wrong:
+        raise ValueError("load_vgg16(%s): missing %s; wrong shape %s" % (type(module).__name__, missing or "none", wrong or "none"))
+    with torch.no_grad():
+        for _, p, v in plan:
+            p.copy_(v.to(p.dtype))
+    if hasattr(module, "invalidate"):
+        module.invalidate()
+    return [name for name, _, _ in plan]

@@ -3,6 +3,7 @@ with torch (device memory + current stream are torch's: plumbing, not compute), 
 Every function raises on CPU tensors -- the HIP kernels are the only implementation."""
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -309,11 +310,54 @@ class PackCache:
 PACK_CACHE = None   # the PackCache of the training step in progress (None: every packed_for() packs)
 
 
+class FrozenPacks:
+    """Packed filters of FROZEN convs (a loss network's trunk) for the autograd conv nodes: packed on first use per (precision, direction,
+    tile) and kept -- nothing re-packs them per step, unlike a PackCache entry.  Alive for as long as its owner holds it (packed_for() sees
+    it through a weak set, in the forward and in a backward that runs after the owner's forward returned).  The filters are held by weak
+    reference, not by address: a weight is served only while the filter it was registered as is alive and still lies at that address with
+    that shape (whatever reaches the node -- the parameter, a detached view -- then aliases it), so a filter whose storage was replaced
+    (`p.data = ...`) or a new tensor that reuses a freed address finds nothing here; an in-place change (load_state_dict) is seen through
+    the filter's version counter and packs again."""
+
+    def __init__(self, params):
+        self.filters = [weakref.ref(p) for p in params if p.dim() == 4]
+        self.entries = {}          # (precision, index in filters, dgrad_pad, cout_tile) -> (data_ptr, version, PackedConv)
+        _FROZEN_PACKS.add(self)
+
+    def _index(self, weight):
+        at, shape = weight.data_ptr(), weight.shape
+        for i, ref in enumerate(self.filters):
+            p = ref()
+            if p is not None and p.data_ptr() == at and p.shape == shape:
+                return i, p
+        return None, None
+
+    def get(self, weight, bias, dgrad_pad, cout_tile=0):
+        if not weight.is_contiguous() or weight.dtype != torch.float32:
+            return None
+        i, p = self._index(weight)
+        if p is None:
+            return None
+        key = (precision(), i, dgrad_pad, cout_tile)
+        hit = self.entries.get(key)
+        if hit is None or hit[0] != p.data_ptr() or hit[1] != p._version:
+            hit = self.entries[key] = (p.data_ptr(), p._version, PackedConv(weight, None, dgrad_pad=dgrad_pad, cout_tile=cout_tile))
+        hit[2].bias = _f32(bias)      # at every call, as PackCache.get
+        return hit[2]
+
+
+_FROZEN_PACKS = weakref.WeakSet()
+
+
 def packed_for(weight, bias=None, dgrad_pad=None, cout_tile=0):
     """The packed image of a conv filter for the autograd nodes: from the step's PackCache when the filter is a trainable parameter
     it knows, packed on the spot otherwise."""
     if PACK_CACHE is not None:
         pc = PACK_CACHE.get(weight, bias, dgrad_pad, cout_tile)
+        if pc is not None:
+            return pc
+    for frozen in _FROZEN_PACKS:
+        pc = frozen.get(weight, bias, dgrad_pad, cout_tile)
         if pc is not None:
             return pc
     return PackedConv(weight, bias, dgrad_pad=dgrad_pad, cout_tile=cout_tile)

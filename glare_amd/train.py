@@ -394,9 +394,10 @@ class Stage1Trainer:
     clamp would zero the gradient wherever the reconstruction leaves [0, 1].
 
     The reference's `self.loss` is taming's VQLPIPSWithDiscriminator (`self.loss(qloss, x, xrec, optimizer_idx, global_step,
-    last_layer=self.get_last_layer())`, VQModel_arch.py:110-160), which is not part of the reference tree.  Of its three parts LPIPS is
-    NOT built (pretrained VGG weights, unobtainable offline as in stage 3); the patch discriminator with the hinge loss and the adaptive
-    weight are, behind `discriminator=`.  With a discriminator D the step at global step t is
+    last_layer=self.get_last_layer())`, VQModel_arch.py:110-160), which is not part of the reference tree.  All three of its parts are
+    built: LPIPS behind `perceptual=losses.LPIPSLoss()` (the VGG16 trunk and the heads are the caller's files, losses.load_vgg16: the
+    pretrained weights cannot be fetched offline, as in stage 3), the patch discriminator with the hinge loss and the adaptive weight
+    behind `discriminator=`.  With a discriminator D the step at global step t is
         nll      = l1 (+ perceptual)                       g_loss = -mean D(xrec)
         d_weight = clamp(|d nll / d W_last| / (|d g_loss / d W_last| + 1e-4), 0, 1e4) * disc_weight, detached; W_last = decoder.conv_out.weight
         loss     = nll + d_weight f g_loss + codebook_weight qloss            f = disc_factor if t >= disc_start else 0

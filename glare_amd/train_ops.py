@@ -835,3 +835,49 @@ def hinge_loss(x, mode, want_grad=True):
     check(lib.glare_hinge_loss_f32(ptr(x), x.numel(), HINGE_MODES[mode], ptr(loss), ptr(grad), ptr(ws), nws, stream_handle()),
           "glare_hinge_loss_f32")
     return loss, grad
+
+
+LPIPS_EPS = 1e-10     # normalize_tensor's eps (lpips / taming)
+
+
+def _lpips_args(a, b, w):
+    require_cuda(a, b, w)
+    assert a.dtype == b.dtype == act_dtype() and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape and a.dim() == 4
+    B, H, W, C = a.shape
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() == C
+    return B, H * W, C
+
+
+def lpips_head(a, b, w, eps=LPIPS_EPS):
+    """One LPIPS tap: 16-bit NHWC feature maps a, b and the fp32 head weights w [C] -> fp32 [B], per image the spatial mean of
+    sum_c w_c (a / (|a| + eps) - b / (|b| + eps))_c^2.  Fixed two-level sum."""
+    B, HW, C = _lpips_args(a, b, w)
+    lib = _lib.lib()
+    nws = lib.glare_lpips_head_workspace_bytes(B, HW, C)
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=a.device)
+    out = torch.empty(B, dtype=torch.float32, device=a.device)
+    check(lib.glare_lpips_head_bf16(ptr(a), ptr(b), ptr(w), B, HW, C, eps, ptr(out), ptr(ws), nws, stream_handle()), "glare_lpips_head_bf16")
+    return out
+
+
+def lpips_head_backward(a, b, w, g, eps=LPIPS_EPS):
+    """d (sum_i g[i] out[i]) / d a, 16-bit like a, formed in fp32 and rounded once; g: fp32 [B] on the DEVICE (no host read).  A pixel
+    of `a` that is all zero gets gradient 0."""
+    B, HW, C = _lpips_args(a, b, w)
+    require_cuda(g)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() == B
+    ga = torch.empty_like(a)
+    check(_lib.lib().glare_lpips_head_backward_bf16(ptr(a), ptr(b), ptr(w), B, HW, C, eps, ptr(g), ptr(ga), stream_handle()),
+          "glare_lpips_head_backward_bf16")
+    return ga
+
+
+def image_affine(x, mul, add=None):
+    """fp32 [..., C] -> x * mul[c] (+ add[c]); mul, add: fp32 [C] on the device."""
+    require_cuda(x, mul, add)
+    C = x.shape[-1]
+    assert x.dtype == torch.float32 and x.is_contiguous() and mul.dtype == torch.float32 and mul.is_contiguous() and mul.numel() == C
+    assert add is None or (add.dtype == torch.float32 and add.is_contiguous() and add.numel() == C)
+    y = torch.empty_like(x)
+    check(_lib.lib().glare_image_affine_f32(ptr(x), ptr(mul), ptr(add), ptr(y), x.numel() // C, C, stream_handle()), "glare_image_affine_f32")
+    return y

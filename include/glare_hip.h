@@ -904,6 +904,30 @@ size_t glare_hinge_workspace_bytes(long long n);
 int glare_hinge_loss_f32(const float* x, long long n, int mode, float* loss, float* grad, void* workspace, size_t workspace_bytes,
                          glare_stream_t stream);
 
+/* ---- stage 1, perceptual term: the LPIPS (VGG16) head of the training path (csrc/lpips_ops.hip) -------------------------------------
+ * Replaces, per feature tap, `normalize_tensor` of both feature maps, the squared difference, the 1x1 head `lin` and `spatial_average`
+ * of taming's / the lpips package's LPIPS.forward -- the perceptual part of VQLPIPSWithDiscriminator's nll, which VQModel.training_step
+ * calls as `self.loss(...)` (code/models/modules/VQModel_arch.py:110-160) -- and what autograd derives from them for the reconstruction's
+ * side.  a (from xrec, differentiated), b (from x, constant): dense 16-bit NHWC [B][HW][C], C in {64, 128, 256, 512}; w: fp32 [C].
+ *   na = sqrt(sum_c a_c^2)  nb = sqrt(sum_c b_c^2)  ah = a / (na + eps)  bh = b / (nb + eps)                  (per pixel, fp32)
+ *   out[i] = (1 / HW) sum_pixels sum_c w_c (ah_c - bh_c)^2                                                      (per image, fp32 [B])
+ *   grad_a = (g[i] / HW) (e_c / (na + eps) - a_c s / (na (na + eps)^2)),  e_c = 2 w_c (ah_c - bh_c),  s = sum_c e_c a_c
+ * g: fp32 [B] on the device, the upstream gradient of out (it carries the loss weight, 1 / B and any loss scale); grad_a is formed in fp32
+ * and rounded to 16 bits once.  A pixel of a that is all zero gets grad_a = 0 (autograd: NaN; the derivative is of order 1 / eps).  The
+ * backward recomputes na, nb and s from a and b.  No atomics; every sum's order depends on the shape alone (bitwise reproducible).
+ * workspace: glare_lpips_head_workspace_bytes(B, HW, C) bytes, caller-owned (0: the shape is not one the kernels take).
+ * GLARE_ERR_INVALID: a null pointer, a non-positive size or eps, C % 8 != 0; GLARE_ERR_UNSUPPORTED: another C, B > 65535, HW >= 2^24.
+ * glare_image_affine_f32: y[p][c] = x[p][c] * mul[c] + add[c] (add NULL: the product alone) on fp32 [n_pixels][C]; mul, add fp32 [C] on the
+ *   device.  LPIPS' ScalingLayer on y = 2 x - 1, (y - shift) / scale, as ONE per-channel map (mul = 2 / scale, add = (-1 - shift) / scale),
+ *   and its backward (mul alone).  Not folded into the first conv: that conv pads with zeros, the shifted image's border is not zero. */
+size_t glare_lpips_head_workspace_bytes(int B, long long HW, int C);
+int glare_lpips_head_bf16(const void* a, const void* b, const float* w, int B, long long HW, int C, float eps, float* out, void* workspace,
+                          size_t workspace_bytes, glare_stream_t stream);
+int glare_lpips_head_backward_bf16(const void* a, const void* b, const float* w, int B, long long HW, int C, float eps, const float* g,
+                                   void* grad_a, glare_stream_t stream);
+int glare_image_affine_f32(const float* x, const float* mul, const float* add_or_null, float* y, long long n_pixels, int C,
+                           glare_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,12 @@ warmed up first.  `python tools/stage1_time.py [--out profiles/stage1_step.txt]`
 `--gan`: instead, the same step with and without the patch discriminator (disc_start = 0) in one session, and every launch the discriminator
 adds timed alone at the step's shapes (8 = 4 real + 4 fake images, two batch groups); for the four 64-to-512-channel conv layers the share of
 the dense 16-bit peak their forward, data-gradient and weight-gradient launches reach.
-`python tools/stage1_time.py --gan [--out profiles/stage1_gan_step.txt]`"""
+`python tools/stage1_time.py --gan [--out profiles/stage1_gan_step.txt]`
+
+`--lpips`: the same step without the term, with the LPIPS term (losses.LPIPSLoss on seeded weights), with the discriminator, and with both,
+in one session; then the LPIPS head's two kernels alone at every tap of that step (the largest: 4 x 256 x 256 x 64) in GB/s of the bytes
+they must move (forward: a and b read once; backward: a and b read, da written).
+`python tools/stage1_time.py --lpips [--out profiles/stage1_lpips_step.txt]`"""
 import argparse
 import os
 import sys
@@ -121,16 +126,90 @@ def gan(args):
     return lines
 
 
+def seeded_lpips(dev, seed=1):
+    """LPIPSLoss on name-seeded weights in a regime where every tap carries signal (filters at He's gain, non-negative heads)."""
+    import math
+
+    from glare_amd import losses
+
+    net = seeded_init_(losses.LPIPSLoss(), seed)
+    const = losses.LPIPSLoss().state_dict()
+    with torch.no_grad():
+        for k, v in net.state_dict().items():
+            if k.startswith("scaling_layer."):
+                v.copy_(const[k])
+            elif k.startswith("net.") and k.endswith(".weight"):
+                v.mul_(math.sqrt(6.0))
+            elif k.startswith("lin"):
+                v.copy_(v.abs() * math.sqrt(v.shape[1]))
+    return net.to(dev)
+
+
+def lpips(args):
+    """The fp16 step at 4 x 3 x 256^2: plain, + LPIPS, + discriminator, + both; then the head's kernels per tap."""
+    from glare_amd import ops
+    from glare_amd import train_ops as T
+
+    dev = torch.device("cuda", 0)
+    lines = ["stage 1 with the LPIPS term on %s (tools/stage1_time.py --lpips; device events, warmed up, ms; one session)"
+             % torch.cuda.get_device_name(0)]
+    x = torch.rand(4, 3, 256, 256, generator=torch.Generator().manual_seed(0)).to(dev)
+    res = {}
+    for name, with_lpips, with_gan in (("plain", False, False), ("lpips", True, False), ("gan", False, True), ("lpips + gan", True, True)):
+        torch.manual_seed(0)
+        disc = M.NLayerDiscriminator().to(dev) if with_gan else None
+        tr = Stage1Trainer(seeded_init_(M.VQModel().train(), 1).to(dev), precision="fp16", discriminator=disc, disc_start=0,
+                           perceptual=seeded_lpips(dev) if with_lpips else None)
+        tr.opt.scale.fill_(1024.0)
+        if disc is not None:
+            tr.opt_d.scale.fill_(1024.0)
+        res[name] = timed(lambda: tr.step_tensor(x), args.steps, warm=3)
+        lines.append("Stage1Trainer.step_tensor fp16, 4 x 3 x 256 x 256, %-11s (eager, %d steps): %.2f ms per step, generator steps applied %d of %d"
+                     % (name, args.steps, res[name], tr.opt.t, args.steps + 3))
+        del tr
+    lines.append("the LPIPS term's share: %.2f ms without the discriminator, %.2f ms with it" % (res["lpips"] - res["plain"], res["lpips + gan"] - res["gan"]))
+    lines.append("the parent commit's profiles/stage1_gan_step.txt has 34.4 ms (plain) / 39.3 ms (gan) from another session: re-measured above, quoted not compared")
+    lines.append("")
+    lines.append("the LPIPS head's kernels alone at the step's taps, fp16, %d launches each (forward: 2 launches; GB/s of the bytes that must move):" % args.reps)
+    lines.append("through the Python wrappers (train_ops: three allocations per forward, one per backward) | the C entry points on preallocated buffers")
+    lines.append("  %-22s %10s %10s %10s %10s | %10s %10s %10s %10s" % (("tap B x H x W x C",) + ("fwd ms", "fwd GB/s", "bwd ms", "bwd GB/s") * 2))
+    from glare_amd import _lib
+
+    with ops.use_precision("fp16"), torch.no_grad():
+        lib, sh = _lib.lib(), _lib.stream_handle
+        g = torch.Generator().manual_seed(1)
+        for side, C in ((256, 64), (128, 128), (64, 256), (32, 512), (16, 512)):
+            a = torch.relu(torch.randn(4, side, side, C, generator=g)).to(dev).to(ops.act_dtype())
+            b = torch.relu(torch.randn(4, side, side, C, generator=g)).to(dev).to(ops.act_dtype())
+            w, gi = torch.rand(C, generator=g).to(dev), torch.full((4,), 256.0, device=dev)
+            fwd = timed(lambda: T.lpips_head(a, b, w), args.reps)
+            bwd = timed(lambda: T.lpips_head_backward(a, b, w, gi), args.reps)
+            nbytes = a.numel() * 2
+            nws = lib.glare_lpips_head_workspace_bytes(4, side * side, C)
+            ws, out, da = torch.empty(nws, dtype=torch.uint8, device=dev), torch.empty(4, device=dev), torch.empty_like(a)
+            p = lambda t: t.data_ptr()
+            cfwd = timed(lambda: lib.glare_lpips_head_bf16(p(a), p(b), p(w), 4, side * side, C, T.LPIPS_EPS, p(out), p(ws), nws, sh()), args.reps)
+            cbwd = timed(lambda: lib.glare_lpips_head_backward_bf16(p(a), p(b), p(w), 4, side * side, C, T.LPIPS_EPS, p(gi), p(da), sh()), args.reps)
+            assert torch.equal(out, T.lpips_head(a, b, w)) and torch.equal(da, T.lpips_head_backward(a, b, w, gi))
+            lines.append("  %-22s %10.4f %10.0f %10.4f %10.0f | %10.4f %10.0f %10.4f %10.0f" % (
+                "4 x %d x %d x %d" % (side, side, C), fwd, 2 * nbytes / fwd / 1e6, bwd, 3 * nbytes / bwd / 1e6,
+                cfwd, 2 * nbytes / cfwd / 1e6, cbwd, 3 * nbytes / cbwd / 1e6))
+    lines.append("(the project's other streaming passes on this box: GroupNorm apply 4.8-5.3 TB/s, VERDICT r06; the forward is its two launches together;")
+    lines.append(" from the third tap down the launches move under 17 MB and are launch-bound)")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=None)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--gan", action="store_true", help="time the step with and without the patch discriminator, and its launches alone")
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--lpips", action="store_true", help="time the step with and without the LPIPS term (and --gan on top), and the head's kernels")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
-    if args.gan:
-        text = "\n".join(gan(args)) + "\n"
+    if args.gan or args.lpips:
+        text = "\n".join((lpips if args.lpips else gan)(args)) + "\n"
         print(text, end="")
         if args.out:
             with open(args.out, "w") as f:
