@@ -663,7 +663,13 @@ __global__ void gradscaler_update_kernel(float* __restrict__ scale, int* __restr
     *tracker = 0;
   } else {
     const int t = *tracker + 1;
-    if (t == interval) { *scale *= growth; *tracker = 0; } else { *tracker = t; }
+    if (t == interval) {
+      const float ns = *scale * growth;   // ATen's _amp_update_scale_: a grown scale that is not finite is not stored (inf would skip every later step)
+      if ((__float_as_uint(ns) & 0x7f800000u) != 0x7f800000u) *scale = ns;
+      *tracker = 0;
+    } else {
+      *tracker = t;
+    }
   }
 }
 
