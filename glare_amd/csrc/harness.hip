@@ -307,6 +307,104 @@ __global__ void score_final_kernel(const unsigned long long* __restrict__ sse_pa
   sse[b] = (long long)s;
 }
 
+// ---- tiled enhancement (glare_amd.enhance.enhance_tiled): overlapping windows of one image, feathered back together ----------
+// uint8 HWC [H][W][3] -> fp32 NCHW [n][3][th][tw]: window t starts at image coordinate (origins[2t], origins[2t + 1]), which may
+// lie outside the image; such coordinates fold as pre_pad_kernel folds them, and the value is its expression, so a window that
+// describes the pixels of a padded image carries that kernel's bits.  One thread per output value, 64-bit element offsets.
+__global__ __launch_bounds__(256) void tile_gather_kernel(const uint8_t* __restrict__ img, int H, int W, const int* __restrict__ origins,
+                                                          int n, int th, int tw, int mode, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long plane = (long long)th * tw;
+  if (i >= (long long)n * 3 * plane) return;
+  const long long tc = i / plane, r = i - tc * plane;
+  const int y = (int)(r / tw), x = (int)(r - (long long)y * tw);
+  const int t = (int)(tc / 3), c = (int)(tc - 3LL * t);
+  const int ys = fold_index((long long)origins[2 * t] + y, H, mode), xs = fold_index((long long)origins[2 * t + 1] + x, W, mode);
+  const float v = (float)img[((long long)ys * W + xs) * 3 + c];
+  out[i] = logf(fmaxf(__fdiv_rn(v, 255.f) + 1e-3f, 1e-3f));
+}
+
+constexpr int HBT = 512;  // blocks of the blend (one int partial each: glare_harness_tile_blend_workspace_bytes)
+
+// The network outputs of an image's n_ty x n_tx windows, fp32 NCHW [n_ty * n_tx][3][th][tw], window (i, j) at image coordinate
+// (y0[i], x0[j]) -> the blended image: acc = sum_i sum_j fmaf(wy_i * wx_j, clamp(v_ij, 0, 1), acc), i and j ascending over the
+// windows that cover the pixel, then (uint8)(fminf(acc, 1) * 255) as post_u8_kernel quantises.  Per axis and per coordinate the host
+// supplies the first covering window, their number (<= 3) and their normalised weights (fc: int32 [L][2], wt: fp32 [L][3]), so the
+// kernel divides nothing; a window the tables name but that does not hold the coordinate is skipped, never read.  post_u8_kernel's
+// layout: the output is one flat byte array and each thread owns one aligned 4-byte word of it (and the 16 bytes of the optional
+// fp32 image at the same element offset).  The count of raw inf / NaN values is an integer sum through one partial per block.
+__global__ __launch_bounds__(256) void tile_blend_kernel(const float* __restrict__ tiles, int n_ty, int n_tx, int th, int tw,
+                                                         const int* __restrict__ y0, const int* __restrict__ x0, int H, int W,
+                                                         const int* __restrict__ row_fc, const float* __restrict__ row_wt,
+                                                         const int* __restrict__ col_fc, const float* __restrict__ col_wt,
+                                                         uint8_t* __restrict__ dst, float* __restrict__ dst_f32,
+                                                         int* __restrict__ bad_partial) {
+  __shared__ int red[4];
+  const long long total = 3LL * H * W, words = (total + 3) / 4;
+  const long long plane = (long long)th * tw;
+  int bad = 0;
+  for (long long wd = (long long)blockIdx.x * 256 + threadIdx.x; wd < words; wd += (long long)HBT * 256) {
+    const long long k0 = wd * 4;
+    const long long p = k0 / 3;
+    int c = (int)(k0 - 3 * p);
+    int y = (int)(p / W), x = (int)(p - (long long)y * W);
+    const int nb = total - k0 < 4 ? (int)(total - k0) : 4;
+    uint32_t word = 0;
+    float a4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < nb) {
+        const int fy = row_fc[2LL * y], ny = row_fc[2LL * y + 1], fx = col_fc[2LL * x], nx = col_fc[2LL * x + 1];
+        float acc = 0.f;
+        for (int a = 0; a < ny && a < 3; ++a) {
+          const int ti = fy + a;
+          if (ti < 0 || ti >= n_ty) continue;
+          const int ly = y - y0[ti];
+          if (ly < 0 || ly >= th) continue;
+          const float wy = row_wt[3LL * y + a];
+          for (int b = 0; b < nx && b < 3; ++b) {
+            const int tj = fx + b;
+            if (tj < 0 || tj >= n_tx) continue;
+            const int lx = x - x0[tj];
+            if (lx < 0 || lx >= tw) continue;
+            const float v = tiles[(((long long)ti * n_tx + tj) * 3 + c) * plane + (long long)ly * tw + lx];
+            bad += (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;   // inf or NaN, counted BEFORE the clamp, once per window
+            acc = fmaf(wy * col_wt[3LL * x + b], fminf(fmaxf(v, 0.f), 1.f), acc);   // fmaxf(NaN, 0) = 0
+          }
+        }
+        a4[j] = acc;
+        word |= (uint32_t)(uint8_t)(fminf(acc, 1.f) * 255.f) << (8 * j);
+        if (++c == 3) { c = 0; if (++x == W) { x = 0; ++y; } }
+      }
+    }
+    if (nb == 4) {
+      *reinterpret_cast<uint32_t*>(dst + k0) = word;
+      if (dst_f32) *reinterpret_cast<float4*>(dst_f32 + k0) = make_float4(a4[0], a4[1], a4[2], a4[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {       // the last word of the image: 1 to 3 bytes
+        if (j < nb) {
+          dst[k0 + j] = (uint8_t)(word >> (8 * j));
+          if (dst_f32) dst_f32[k0 + j] = a4[j];
+        }
+      }
+    }
+  }
+  if (!bad_partial) return;
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) bad_partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ void tile_blend_count_kernel(const int* __restrict__ bad_partial, int* __restrict__ nonfinite) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    int s = 0;
+    for (int k = 0; k < HBT; ++k) s += bad_partial[k];
+    *nonfinite = s;
+  }
+}
+
 }  // namespace
 
 // restored float in [0,1] -> uint8 = rint(clip * 255): img_as_ubyte(restored), the image the reference's loop hands to imwrite
@@ -432,5 +530,38 @@ extern "C" int glare_harness_score_u8(const float* out_nchw, const float* gain_o
   hipLaunchKernelGGL(score_u8_kernel, dim3(HBS, B), dim3(256), 0, s, out_nchw, gain_or_null, gt_hwc, B, Hp, Wp, top, left, h, w, out_hwc_u8,
                      sse_partial);
   hipLaunchKernelGGL(score_final_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, sse_partial, B, sse);
+  return glare_launch_status();
+}
+
+extern "C" int glare_harness_tile_gather_u8(const unsigned char* img_hwc, int H, int W, const int* origins_yx, int n, int th, int tw, int mode,
+                                            float* out_nchw, glare_stream_t stream) {
+  if (!img_hwc || !origins_yx || !out_nchw || H <= 0 || W <= 0 || n <= 0 || th <= 0 || tw <= 0) return GLARE_ERR_INVALID;
+  if (mode != GLARE_PAD_REFLECT101 && mode != GLARE_PAD_SYMMETRIC) return GLARE_ERR_INVALID;
+  if ((long long)th * tw > 0x7fffffffLL * 256 / 3 / n) return GLARE_ERR_INVALID;      // one thread per value, at most 2^31 - 1 blocks
+  const long long blocks = cdivll((long long)n * 3 * th * tw, 256);
+  hipLaunchKernelGGL(tile_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), img_hwc, H, W, origins_yx,
+                     n, th, tw, mode, out_nchw);
+  return glare_launch_status();
+}
+
+extern "C" size_t glare_harness_tile_blend_workspace_bytes(void) { return (size_t)HBT * sizeof(int); }
+
+extern "C" int glare_harness_tile_blend_f32(const float* tiles_nchw, int n_ty, int n_tx, int th, int tw, const int* y0, const int* x0, int H,
+                                            int W, const int* row_first_count, const float* row_weight, const int* col_first_count,
+                                            const float* col_weight, unsigned char* out_hwc_u8, float* out_hwc_f32_or_null,
+                                            int* nonfinite_or_null, void* workspace, size_t workspace_bytes, glare_stream_t stream) {
+  if (!tiles_nchw || !y0 || !x0 || !row_first_count || !row_weight || !col_first_count || !col_weight || !out_hwc_u8) return GLARE_ERR_INVALID;
+  if (n_ty <= 0 || n_tx <= 0 || th <= 0 || tw <= 0 || H <= 0 || W <= 0) return GLARE_ERR_INVALID;
+  if ((long long)n_ty * n_tx > 0x7fffffffLL) return GLARE_ERR_INVALID;
+  if (((uintptr_t)out_hwc_u8 & 3) || ((uintptr_t)out_hwc_f32_or_null & 15)) return GLARE_ERR_INVALID;    // written as 4- and 16-byte words
+  int* bad_partial = nullptr;
+  if (nonfinite_or_null) {
+    if (!workspace || workspace_bytes < glare_harness_tile_blend_workspace_bytes()) return GLARE_ERR_WORKSPACE;
+    bad_partial = static_cast<int*>(workspace);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(tile_blend_kernel, dim3(HBT), dim3(256), 0, s, tiles_nchw, n_ty, n_tx, th, tw, y0, x0, H, W, row_first_count, row_weight,
+                     col_first_count, col_weight, out_hwc_u8, out_hwc_f32_or_null, bad_partial);
+  if (nonfinite_or_null) hipLaunchKernelGGL(tile_blend_count_kernel, dim3(1), dim3(64), 0, s, bad_partial, nonfinite_or_null);
   return glare_launch_status();
 }

@@ -2,12 +2,15 @@
 code/infer_unpaired.py:91-136 on the HIP path.
 
     python -m glare_amd.enhance photos/ more/img.png --out enhanced/ [--net-g G.pth --net-vq VQ.pth --precision fp16 --batch 8]
+                                [--tile 512 --tile-overlap 64]
 
 Per image, the reference's steps: read as RGB uint8 (cv2.imread, :47), auto_padding to a multiple of 16 with cv2.BORDER_REFLECT
 (:81-88), /255, log(clamp(x + 1e-3, min=1e-3)) (:39, :122), the network (get_sr, :128), crop + clamp + rgb() -- which truncates
 (:42, :129-130) -- and imwrite under the same basename (:136).  Padding, the log transform, the crop and the uint8 conversion run on
 the device (csrc/harness.hip): images cross PCIe as uint8 both ways.  Images of one padded shape are enhanced in batches; the size
-envelope of the kernels (SIZE_TABLE) is checked before anything is launched.  Without checkpoints the weights are name-seeded."""
+envelope of the kernels (SIZE_TABLE) is checked before anything is launched; with --tile, an image larger than a tile is enhanced
+as overlapping tiles that are feathered together on the device, so its size is bounded by memory alone.  Without checkpoints the
+weights are name-seeded."""
 import argparse
 import glob
 import json
@@ -69,6 +72,116 @@ def max_batch(hp, wp, cap=1 << 16):
             break
         b += 1
     return b
+
+
+# ---- the tile plan ----------------------------------------------------------------------------------------------------------
+# An image with a side longer than `tile` is enhanced as overlapping windows of one shape that are feathered back together
+# (DESIGN.md "Tiled enhancement"): each window stays inside the size envelope and near the token count the network was trained at.
+def plan_axis(L, tile, overlap):
+    """One axis of the plan -> (starts, length, keep0): the image coordinate of each window's first pixel, the windows' common
+    length, and the offset inside the first window at which image coordinate 0 lies.  L <= tile: one window [-p1, L + p2) with
+    auto_padding's (p1, p2) -- the axis exactly as the untiled path pads it.  L > tile: windows of `tile` pixels every tile - overlap,
+    the last one shifted back to end at L; every window lies inside the image, nothing is padded, up to three cover a coordinate."""
+    if L < 1 or tile < 16 or tile % 16 != 0 or overlap < 16 or tile < 2 * overlap:
+        raise ValueError("tile plan: L = %d, tile = %d, overlap = %d (need L >= 1, tile a multiple of 16, overlap >= 16, tile >= 2 * overlap)"
+                         % (L, tile, overlap))
+    if L <= tile:
+        p1, p2 = harness.auto_padding(L, L)[:2]
+        return [-p1], L + p1 + p2, p1
+    stride = tile - overlap
+    n = -(-(L - overlap) // stride)
+    return [min(i * stride, L - tile) for i in range(n)], tile, 0
+
+
+def axis_weights(L, starts, length, overlap):
+    """The blend table of one axis -> (first int32 [L], count int32 [L], weight fp32 [L,3]): per image coordinate the first window
+    that covers it, the number of covering windows (consecutive, <= 3) and their weights.  Window i of n ramps over the REQUESTED
+    overlap O, whatever its actual overlap with the neighbour: r_i(x) = min(1, (x + 0.5 - s_i) / O if i > 0, (s_i + length - x - 0.5) / O
+    if i < n - 1); weight = r_i / sum_k r_k in fp64, rounded once to fp32 (a lone window: exactly 1)."""
+    n = len(starts)
+    x = np.arange(L, dtype=np.float64)
+    r = np.zeros((n, L), dtype=np.float64)
+    for i, s in enumerate(starts):
+        ri = np.ones(L, dtype=np.float64)
+        if i > 0:
+            ri = np.minimum(ri, (x + 0.5 - s) / overlap)
+        if i < n - 1:
+            ri = np.minimum(ri, (s + length - x - 0.5) / overlap)
+        r[i] = np.where((x >= s) & (x < s + length), ri, 0.0)
+    cover = r > 0
+    count = cover.sum(axis=0)
+    first = cover.argmax(axis=0)
+    assert count.min() >= 1 and count.max() <= 3, "tile plan: a coordinate is covered by %d..%d windows" % (count.min(), count.max())
+    norm = r / r.sum(axis=0)
+    weight = np.zeros((L, 3), dtype=np.float32)
+    cols = np.arange(L)
+    for a in range(3):
+        sel = count > a
+        weight[sel, a] = norm[np.minimum(first + a, n - 1), cols][sel].astype(np.float32)
+    return first.astype(np.int32), count.astype(np.int32), weight
+
+
+def plan_tiles(h, w, tile=512, overlap=64, name=None):
+    """The plan of an h x w image: window origins per axis (ys, xs), the windows' shape (th, tw), where image coordinate (0, 0) lies
+    in the first window (keep) and the two blend tables.  check_size() refuses a window shape outside the envelope before any launch."""
+    ys, th, ky = plan_axis(h, tile, overlap)
+    xs, tw, kx = plan_axis(w, tile, overlap)
+    check_size(th, tw, 1, name)
+    return {"h": h, "w": w, "tile": tile, "overlap": overlap, "ys": ys, "xs": xs, "th": th, "tw": tw, "keep": (ky, kx),
+            "row_table": axis_weights(h, ys, th, overlap), "col_table": axis_weights(w, xs, tw, overlap)}
+
+
+def enhance_tiled(img_u8, netG=None, net_vq=None, tile=512, overlap=64, precision=None, batch=8, tile_fn=None, blend_fn=None,
+                  device=None, report=None, name=None):
+    """uint8 [h,w,3] of any size -> the enhanced uint8 [h,w,3], through overlapping windows of plan_tiles(h, w, tile, overlap).
+
+    The image is uploaded once as uint8; its windows are gathered on the device into the log domain (harness.tile_gather_device), run
+    through netG.reverse_flow_nhwc in batches of min(batch, max_batch(th, tw)) -- all windows share one shape --, their fp32 outputs
+    stay on the device and one launch blends, clamps and truncates them to uint8 (harness.tile_blend_device).  If any window value
+    inside the image is inf / NaN and the precision is not bf16, all windows run again in bf16 (report["bf16_rerun"] = True).
+    tile_fn(lr fp32 [n,3,th,tw] log domain, precision) -> network outputs of the same shape, and blend_fn(outputs [N,3,th,tw], plan) ->
+    (uint8 [h,w,3], non-finite count) replace the network and the blend with host code (both or neither); the windows are then cut
+    by harness.tile_gather.  report: a dict that receives "tiles" = [n_ty, n_tx], "tile_shape", "nonfinite" and "bf16_rerun"."""
+    assert img_u8.dtype == np.uint8 and img_u8.ndim == 3 and img_u8.shape[2] == 3, (name, img_u8.dtype, img_u8.shape)
+    if (tile_fn is None) != (blend_fn is None):
+        raise ValueError("enhance_tiled: tile_fn and blend_fn replace the device path together")
+    h, w = img_u8.shape[:2]
+    plan = plan_tiles(h, w, tile, overlap, name)
+    th, tw = plan["th"], plan["tw"]
+    origins = [(y, x) for y in plan["ys"] for x in plan["xs"]]
+    n = len(origins)
+    bs = max(1, min(batch, max_batch(th, tw)))
+    if tile_fn is not None:
+        lr = harness.tile_gather(img_u8, origins, th, tw)
+
+        def once(prec):
+            outs = np.concatenate([np.asarray(tile_fn(lr[s:s + bs], prec), dtype=np.float32) for s in range(0, n, bs)])
+            return blend_fn(outs, plan)
+    else:
+        import torch
+
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        src = _stack([img_u8])
+        img_d = (src if isinstance(src, torch.Tensor) else torch.from_numpy(src))[0].to(device, non_blocking=True)      # uint8, once
+        origins_d = torch.tensor(origins, dtype=torch.int32).to(device)
+        tables = harness.tile_blend_tables(plan, device)
+
+        def once(prec):
+            outs = torch.empty(n, 3, th, tw, dtype=torch.float32, device=device)
+            with torch.no_grad():
+                for s in range(0, n, bs):
+                    lr = harness.tile_gather_device(img_d, origins_d[s:s + bs], th, tw)
+                    outs[s:s + bs].copy_(netG.reverse_flow_nhwc(net_vq, lr, precision=prec)["out"])
+            u8, _, bad = harness.tile_blend_device(outs, plan, tables)
+            return u8.cpu().numpy(), int(bad.cpu())
+
+    out, bad = once(precision)
+    rerun = int(bad) > 0 and precision != "bf16"       # fp16 overflow: bf16 has fp32's range, same kernels
+    if rerun:
+        out, bad = once("bf16")
+    if report is not None:
+        report.update(tiles=[len(plan["ys"]), len(plan["xs"])], tile_shape=[th, tw], nonfinite=int(bad), bf16_rerun=rerun)
+    return out
 
 
 # ---- reading and writing ----------------------------------------------------------------------------------------------------
@@ -140,32 +253,49 @@ def device_enhance_fn(netG, net_vq, device):
     return fn
 
 
-def enhance_images(imgs, netG=None, net_vq=None, precision=None, batch=8, enhance_fn=None, names=None, device=None, report=None):
+def enhance_images(imgs, netG=None, net_vq=None, precision=None, batch=8, enhance_fn=None, names=None, device=None, report=None,
+                   tile=None, overlap=64, tile_fn=None, blend_fn=None):
     """uint8 HWC arrays of any sizes -> the enhanced uint8 arrays, same shapes, same order.
 
     Images are grouped by padded shape and each group runs in batches of at most `batch`, capped by max_batch() (the DCN fast path's
     whole-batch extents).  check_size() refuses an image outside the envelope with ValueError before anything is launched.
     enhance_fn(batch_u8 [n,H,W,3], pads, precision) -> (uint8 [n,H,W,3], nonfinite [n]): the network call (default: the HIP path
     over netG / net_vq).  An image whose fp16 output holds inf / NaN before the clamp is run again in bf16 and named in
-    report["bf16_rerun_images"] (as glare_amd.infer does).  report: a dict that receives that list and per-image padded sizes."""
+    report["bf16_rerun_images"] (as glare_amd.infer does).  report: a dict that receives that list and per-image padded sizes.
+    tile: an image with a side longer than `tile` goes through enhance_tiled(tile, overlap, tile_fn, blend_fn) instead -- one image at
+    a time, its windows batched; report["tiles"] maps its name to [n_ty, n_tx] and its "padded" entry is the windows' shape.  Without
+    `tile` nothing is tiled and such an image is refused as before."""
     names = list(names) if names is not None else ["#%d" % i for i in range(len(imgs))]
-    shapes = []
-    for nm, im in zip(names, imgs):
+    shapes, tiled = [], {}
+    for i, (nm, im) in enumerate(zip(names, imgs)):
         assert im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3, (nm, im.dtype, im.shape)
+        if tile is not None and max(im.shape[:2]) > tile:
+            tiled[i] = plan_tiles(im.shape[0], im.shape[1], tile, overlap, nm)       # raises before any launch, as check_size does
+            shapes.append((tiled[i]["th"], tiled[i]["tw"], None))
+            continue
         pads = harness.auto_padding(im.shape[0], im.shape[1])
         hp, wp = im.shape[0] + pads[0] + pads[1], im.shape[1] + pads[2] + pads[3]
         check_size(hp, wp, 1, nm)
         shapes.append((hp, wp, pads))
-    if enhance_fn is None:
+    if enhance_fn is None and len(tiled) < len(imgs):
         import torch
 
         device = device or torch.device("cuda", torch.cuda.current_device())
         enhance_fn = device_enhance_fn(netG, net_vq, device)
     groups = {}
     for i, im in enumerate(imgs):
-        groups.setdefault((im.shape[0], im.shape[1]), []).append(i)
+        if i not in tiled:
+            groups.setdefault((im.shape[0], im.shape[1]), []).append(i)
     results = [None] * len(imgs)
-    reruns, per_size = [], {}
+    reruns, per_size, tiles = [], {}, {}
+    for i, plan in tiled.items():
+        t0 = time.perf_counter()
+        rep = {}
+        results[i] = enhance_tiled(imgs[i], netG, net_vq, tile, overlap, precision, batch, tile_fn, blend_fn, device, rep, names[i])
+        tiles[names[i]] = rep["tiles"]
+        if rep["bf16_rerun"]:
+            reruns.append(names[i])
+        per_size["%dx%d" % imgs[i].shape[:2]] = round(time.perf_counter() - t0, 4)       # the result is a host array: synchronous
     for (h, w), idx in groups.items():
         t0 = time.perf_counter()
         hp, wp, pads = shapes[idx[0]]
@@ -184,6 +314,7 @@ def enhance_images(imgs, netG=None, net_vq=None, precision=None, batch=8, enhanc
         report["seconds_per_image_by_size"] = per_size
         report["bf16_rerun_images"] = [n for n in names if n in reruns]
         report["padded"] = [list(s[:2]) for s in shapes]
+        report["tiles"] = tiles
     return results
 
 
@@ -216,9 +347,11 @@ def load_nets(net_g=None, net_vq=None, device=None):
     return netG.to(device), net_vq_m.to(device)
 
 
-def run(inputs, out_dir, netG=None, net_vq=None, precision=None, batch=8, enhance_fn=None, device=None):
+def run(inputs, out_dir, netG=None, net_vq=None, precision=None, batch=8, enhance_fn=None, device=None, tile=None, overlap=64,
+        tile_fn=None, blend_fn=None):
     """Enhance every readable image of `inputs` (files and folders) into out_dir under its basename; -> the result dict of the
-    JSON line (per-image name / size / padded size, skipped files with reasons, bf16 re-runs, seconds, images/s, MP/s)."""
+    JSON line (per-image name / size / padded size, "tiles": [n_ty, n_tx] for an image enhanced in tiles, skipped files with reasons,
+    bf16 re-runs, seconds, images/s, MP/s).  tile / overlap: as enhance_images."""
     files = list_inputs(inputs)
     imgs, names, skipped = [], [], []
     for f in files:
@@ -229,24 +362,25 @@ def run(inputs, out_dir, netG=None, net_vq=None, precision=None, batch=8, enhanc
             imgs.append(img)
             names.append(os.path.basename(f))
     sync = lambda: None
-    if enhance_fn is None:
+    if enhance_fn is None and tile_fn is None:
         import torch
 
         sync = torch.cuda.synchronize
         if imgs:                      # warm-up at the smallest shape: weight packing, workspace growth, kernel loading
             small = min(imgs, key=lambda a: a.shape[0] * a.shape[1])
-            enhance_images([small], netG, net_vq, precision, 1, device=device)
+            enhance_images([small], netG, net_vq, precision, 1, device=device, tile=tile, overlap=overlap)
         sync()
     report = {}
     t0 = time.perf_counter()
-    outs = enhance_images(imgs, netG, net_vq, precision, batch, enhance_fn, names, device, report)
+    outs = enhance_images(imgs, netG, net_vq, precision, batch, enhance_fn, names, device, report, tile, overlap, tile_fn, blend_fn)
     sync()
     secs = time.perf_counter() - t0          # uint8 on the host -> uint8 back on the host (excluding decode / encode of the files)
     for nm, o in zip(names, outs):
         write_image(os.path.join(out_dir, nm), o)
     mp = sum(a.shape[0] * a.shape[1] for a in imgs) / 1e6
-    return {"images": [{"name": n, "size": [int(a.shape[0]), int(a.shape[1])], "padded": p} for n, a, p in
-                       zip(names, imgs, report.get("padded", []))],
+    tiles = report.get("tiles", {})
+    return {"images": [dict({"name": n, "size": [int(a.shape[0]), int(a.shape[1])], "padded": p}, **({"tiles": tiles[n]} if n in tiles else {}))
+                       for n, a, p in zip(names, imgs, report.get("padded", []))],
             "skipped": skipped, "bf16_rerun_images": report.get("bf16_rerun_images", []),
             "seconds": round(secs, 4), "seconds_per_image_by_size": report.get("seconds_per_image_by_size", {}), "images_per_sec": round(len(imgs) / secs, 3) if imgs and secs > 0 else 0.0,
             "megapixels_per_sec": round(mp / secs, 3) if imgs and secs > 0 else 0.0,
@@ -262,13 +396,17 @@ def main(argv=None):
     ap.add_argument("--precision", choices=("fp16", "bf16"), default=None,
                     help="16-bit format of activations and filters (default fp16; images whose fp16 output is not finite are re-run in bf16)")
     ap.add_argument("--batch", type=int, default=8, help="images of one padded size per launch (capped by the size envelope)")
+    ap.add_argument("--tile", type=int, default=None, metavar="N",
+                    help="enhance an image with a side longer than N pixels as overlapping N x N tiles that are feathered together (a multiple of 16, "
+                         "e.g. 512); without it such an image must fit the kernels' size envelope (about 4 MP)")
+    ap.add_argument("--tile-overlap", type=int, default=64, metavar="O", help="overlap of neighbouring tiles in pixels (>= 16, at most N / 2)")
     args = ap.parse_args(argv)
     import torch
 
     assert torch.cuda.is_available(), "glare_amd.enhance needs an MI355X: the HIP kernels are the only implementation"
     device = torch.device("cuda", torch.cuda.current_device())
     netG, net_vq = load_nets(args.net_g, args.net_vq, device)
-    res = run(args.inputs, args.out, netG, net_vq, args.precision, max(1, args.batch), device=device)
+    res = run(args.inputs, args.out, netG, net_vq, args.precision, max(1, args.batch), device=device, tile=args.tile, overlap=args.tile_overlap)
     print(json.dumps(res))
     return res
 

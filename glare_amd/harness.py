@@ -161,6 +161,75 @@ def postprocess_unpaired_device(out_nchw, pads, h, w, want_nonfinite=False):
     return (u8, bad) if want_nonfinite else u8
 
 
+# ---- tiled enhancement (glare_amd.enhance.enhance_tiled): overlapping windows of one image, feathered together --------------------
+def tile_gather_device(img_u8, origins, th, tw, mode=PAD_SYMMETRIC):
+    """uint8 device tensor [H,W,3] and int32 device tensor [n,2] of window origins (y0, x0; may be negative) -> fp32 [n,3,th,tw] in
+    the log domain; coordinates outside the image fold as preprocess_unpaired_device pads, and the arithmetic is the same."""
+    _lib.require_cuda(img_u8, origins)
+    assert img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3 and img_u8.is_contiguous()
+    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()
+    H, W, _ = img_u8.shape
+    n = origins.shape[0]
+    out = torch.empty(n, 3, th, tw, dtype=torch.float32, device=img_u8.device)
+    _lib.check(_lib.main_lib().glare_harness_tile_gather_u8(_lib.ptr(img_u8), H, W, _lib.ptr(origins), n, th, tw, mode, _lib.ptr(out),
+                                                            _lib.stream_handle()), "glare_harness_tile_gather_u8")
+    return out
+
+
+def tile_blend_tables(plan, device):
+    """The device-side tables of a tile plan (enhance.plan_tiles) as tile_blend_device takes them.  Checked here, on the host: every
+    window an axis table names for a coordinate holds that coordinate, so the kernel reads inside the tile buffer."""
+    tabs = []
+    for starts, length, (first, count, weight), L in ((plan["ys"], plan["th"], plan["row_table"], plan["h"]),
+                                                      (plan["xs"], plan["tw"], plan["col_table"], plan["w"])):
+        s = np.asarray(starts, dtype=np.int64)
+        first, count = np.asarray(first, dtype=np.int64), np.asarray(count, dtype=np.int64)
+        assert first.shape == count.shape == (L,) and np.asarray(weight).shape == (L, 3)
+        assert (count >= 1).all() and (count <= 3).all() and (first >= 0).all() and (first + count <= len(s)).all()
+        x = np.arange(L)
+        for a in range(3):
+            sel = count > a
+            lo = s[np.minimum(first + a, len(s) - 1)]
+            assert ((x >= lo) & (x < lo + length))[sel].all(), "a blend table names a window that does not hold the coordinate"
+        fc = np.ascontiguousarray(np.stack([first, count], axis=1).astype(np.int32))
+        tabs.append((torch.from_numpy(s.astype(np.int32)).to(device), torch.from_numpy(fc).to(device),
+                     torch.from_numpy(np.ascontiguousarray(weight, dtype=np.float32)).to(device)))
+    return tabs
+
+
+def tile_blend_device(tiles, plan, tables=None, want_f32=False):
+    """network outputs fp32 [n_ty*n_tx,3,th,tw] (device) of the windows of `plan` -> (uint8 [h,w,3], fp32 [h,w,3] or None, int32 [1]),
+    all on the device: the feathered blend of the clamped windows truncated to uint8 as rgb() does, the blended value before that
+    (want_f32), and the number of raw inf / NaN window values inside the image."""
+    _lib.require_cuda(tiles)
+    n_ty, n_tx, th, tw, h, w = len(plan["ys"]), len(plan["xs"]), plan["th"], plan["tw"], plan["h"], plan["w"]
+    assert tiles.dtype == torch.float32 and tuple(tiles.shape) == (n_ty * n_tx, 3, th, tw) and tiles.is_contiguous()
+    (y0, rfc, rwt), (x0, cfc, cwt) = tables if tables is not None else tile_blend_tables(plan, tiles.device)
+    lib = _lib.main_lib()
+    nws = lib.glare_harness_tile_blend_workspace_bytes()
+    ws = torch.empty(nws, dtype=torch.uint8, device=tiles.device)
+    u8 = torch.empty(h, w, 3, dtype=torch.uint8, device=tiles.device)
+    f32 = torch.empty(h, w, 3, dtype=torch.float32, device=tiles.device) if want_f32 else None
+    bad = torch.empty(1, dtype=torch.int32, device=tiles.device)
+    _lib.check(lib.glare_harness_tile_blend_f32(_lib.ptr(tiles), n_ty, n_tx, th, tw, _lib.ptr(y0), _lib.ptr(x0), h, w, _lib.ptr(rfc),
+                                                _lib.ptr(rwt), _lib.ptr(cfc), _lib.ptr(cwt), _lib.ptr(u8), _lib.ptr(f32), _lib.ptr(bad),
+                                                _lib.ptr(ws), nws, _lib.stream_handle()), "glare_harness_tile_blend_f32")
+    return u8, f32, bad
+
+
+def tile_gather(img_u8, origins, th, tw):
+    """Host restatement of tile_gather_device (symmetric fold): uint8 [H,W,3] and (y0, x0) origins -> fp32 [n,3,th,tw], log domain."""
+    H, W = img_u8.shape[:2]
+
+    def fold(i, n):                                   # cv2.BORDER_REFLECT at any distance: period 2n
+        p = np.mod(i, 2 * n)
+        return np.where(p < n, p, 2 * n - 1 - p)
+
+    wins = [img_u8[fold(y0 + np.arange(th), H)][:, fold(x0 + np.arange(tw), W)] for y0, x0 in origins]
+    x = torch.from_numpy(np.ascontiguousarray(np.stack(wins).transpose(0, 3, 1, 2)).astype(np.float32)) / 255
+    return torch.log(torch.clamp(x + 1e-3, min=1e-3))
+
+
 def preprocess_unpaired(img_u8, pads=None):
     """Host restatement: uint8 [H,W,3] -> fp32 [1,3,Hp,Wp] in the log domain, auto_padding with numpy 'symmetric' (=
     cv2.BORDER_REFLECT), t() (:39) and log_low (:122)."""

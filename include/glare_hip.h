@@ -781,6 +781,33 @@ int glare_harness_postprocess_u8(const float* out_nchw, int B, int Hp, int Wp, i
                                  unsigned char* out_hwc_u8, int* nonfinite_or_null, void* workspace, size_t workspace_bytes,
                                  glare_stream_t stream);
 
+/* ---- tiled enhancement (glare_amd.enhance.enhance_tiled): an image larger than the kernels' size envelope as overlapping windows ----
+ * Both take ONE image and use 64-bit element offsets throughout (the image and the window buffer may exceed 2^31 B), launch on
+ * `stream`, use no atomics (the same bits from run to run) and return GLARE_ERR_INVALID on bad arguments.
+ * glare_harness_tile_gather_u8: uint8 HWC [H][W][3] (device) -> fp32 NCHW [n][3][th][tw] in the log domain.  origins_yx: int32 [n][2]
+ *   (device), the image coordinate (y0, x0) of each window's first pixel; it may be negative and the window may reach past the image:
+ *   such coordinates fold with `mode` exactly as glare_harness_preprocess_pad_u8 folds them, and the arithmetic is its /255,
+ *   log(clamp(x + 1e-3, min = 1e-3)) -- where the two describe the same pixels (one window at (-top, -left) of the padded size), the
+ *   bits are equal.
+ * glare_harness_tile_blend_f32: the network outputs of the n_ty x n_tx windows of one image, fp32 NCHW [n_ty * n_tx][3][th][tw], window
+ *   (i, j) at image coordinate (y0[i], x0[j]) (int32 [n_ty] / [n_tx], device) -> out_hwc_u8 [H][W][3].  Per axis the host supplies, for
+ *   every image coordinate, the first window that covers it and the number of covering windows (<= 3): row_first_count int32 [H][2],
+ *   col_first_count int32 [W][2]; and their normalised blend weights, fp32 [H][3] / [W][3] (unused slots 0), so the kernel divides
+ *   nothing.  Per window value v = fminf(fmaxf(x, 0), 1) (a NaN becomes 0, as glare_harness_postprocess_u8); acc = sum_i sum_j
+ *   fmaf(wy_i * wx_j, v_ij, acc), i ascending outside and j ascending inside; out = (uint8)(fminf(acc, 1) * 255.0f), truncating as
+ *   rgb() does.  With one window of weight 1 this is glare_harness_postprocess_u8 byte for byte.  A window the tables name but that
+ *   does not hold the coordinate is skipped.  out_hwc_f32_or_null: fp32 HWC [H][W][3], acc before quantisation.  nonfinite_or_null:
+ *   one int32, the raw inf / NaN window values at positions inside the image, each counted once per window that holds it, summed in a
+ *   fixed order through workspace >= glare_harness_tile_blend_workspace_bytes() (which may be NULL without it).  out_hwc_u8 is written
+ *   as 4-byte words and out_hwc_f32 as 16-byte words: aligned accordingly. */
+int glare_harness_tile_gather_u8(const unsigned char* img_hwc, int H, int W, const int* origins_yx, int n, int th, int tw, int mode,
+                                 float* out_nchw, glare_stream_t stream);
+size_t glare_harness_tile_blend_workspace_bytes(void);
+int glare_harness_tile_blend_f32(const float* tiles_nchw, int n_ty, int n_tx, int th, int tw, const int* y0, const int* x0, int H, int W,
+                                 const int* row_first_count, const float* row_weight, const int* col_first_count,
+                                 const float* col_weight, unsigned char* out_hwc_u8, float* out_hwc_f32_or_null, int* nonfinite_or_null,
+                                 void* workspace, size_t workspace_bytes, glare_stream_t stream);
+
 /* ---- the checkpoint sweep's "adjust" protocol (code/test_stage2.py:169-180, code/test_stage3.py:183-185, :203-204) ------------
  * Both read the [h][w] window at (top, left) of the network output fp32 NCHW [B][3][Hp][Wp], as glare_harness_postprocess_u8 takes
  * it, and the uint8 ground truth HWC [B][h][w][3].  B <= 65535, 3 h w < 2^31; workspace >= glare_harness_score_workspace_bytes(B).
