@@ -42,7 +42,43 @@ constexpr float RESCALE_THR = 8.0f;  // log2 units
 // pieces per tile are (~25 %); an 8-wave form (16 query rows per wave on v_mfma_f32_16x16x32, two waves per SIMD): 975-995 vs 1 030-1 045
 // TFLOP/s -- two waves per SIMD do hide the DMA issue cost (8 % instead of 25 %), but every 1-KB fragment then feeds a 16-row MFMA and
 // twice the LDS read traffic per flop (512 KB per 32-key tile per CU) becomes the limit.
-constexpr int ATTN_DMA_PER_GROUP = 2;  // DMA pieces issued per 4-MFMA group (2: all 16 during QK^T; 1, over the whole tile, measured slower)
+constexpr int ATTN_DMA_PER_GROUP = 2;  // attn_fwd_kernel: DMA pieces issued per 4-MFMA group (2: all 16 during QK^T; 1, over the whole tile, measured slower)
+
+// attn_kv_fwd_kernel: where a wave issues the 8 LDS-DMA pieces of the NEXT tile inside the body of the current one -- pieces per slot.
+// Slots 0-7 are the K.Q^T MFMA groups, slot 8 is the softmax section (its pieces go between the exp2 steps, never in one burst), slots
+// 9-16 are the P.V MFMA groups.  Nobody reads the other buffer between two top-of-tile barriers, so every table that sums to 8 computes
+// the same thing; an A/B build chooses one with -DATTN_KV_PLACE=... (no blanks) in GLARE_DEFS.  Measured (profiles/attn_schedule.txt,
+// DESIGN.md section 8): the default below, one piece per K.Q^T group, is the placement kept.
+#ifndef ATTN_KV_PLACE
+#define ATTN_KV_PLACE 1,1,1,1,1,1,1,1,0,0,0,0,0,0,0,0,0
+#endif
+// P.V fragment reads of attn_kv_fwd_kernel: 1 = the two transpose reads of an A-fragment of group g+1 follow each MFMA of group g, so
+// their issue falls into the 32 matrix-pipe cycles of that MFMA; 0 = all 8 reads of group g+1 in one run ahead of group g's four MFMAs
+// (the schedule up to here: the matrix pipe stood idle while the wave issued them -- P.V 1 588 -> 1 284 clock counts per tile,
+// profiles/attn_schedule.txt).  Both read the same data in the same order into the same MFMAs.
+#ifndef ATTN_KV_PV_INTERLEAVE
+#define ATTN_KV_PV_INTERLEAVE 1
+#endif
+constexpr bool KV_PV_INTERLEAVE = ATTN_KV_PV_INTERLEAVE;
+constexpr int KV_SLOTS = 17, KV_SLOT_SOFTMAX = 8, KV_SOFTMAX_STEPS = 8;
+constexpr int KV_PLACE[KV_SLOTS] = {ATTN_KV_PLACE};
+constexpr int kv_place_first(int slot) {   // index of the first piece of `slot` = pieces of all earlier slots
+  int n = 0;
+  for (int s = 0; s < slot; ++s) n += KV_PLACE[s];
+  return n;
+}
+static_assert(kv_place_first(KV_SLOTS) == BN / 4, "ATTN_KV_PLACE must place exactly the 8 pieces of a tile");
+// piece k of the n softmax pieces follows exp2 step k * 8 / n
+constexpr int kv_softmax_pieces_before(int step) {
+  const int n = KV_PLACE[KV_SLOT_SOFTMAX];
+  int c = 0;
+  for (int k = 0; k < n; ++k) c += (k * KV_SOFTMAX_STEPS / (n > 0 ? n : 1) < step);
+  return c;
+}
+constexpr int kv_softmax_valu_per_piece() {
+  const int n = KV_PLACE[KV_SLOT_SOFTMAX];
+  return 56 / (n > 0 ? n : 1);
+}
 
 __device__ __forceinline__ void dma16a(const void* gsrc, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
@@ -71,7 +107,23 @@ struct AttnParams {
   float* part_ml;      // [B][key_splits][N][2]   (running max in log2 units, sum)
   float* lse;          // optional [B][N]: log2 sum_j 2^(q_i.k_j) of every query row (what the backward needs); attn_fwd_kernel only
   a16_t* o_lo;         // optional remainder half of the output (value = o + o_lo, same ldo): attn_kv_fwd_kernel / attn_combine_kernel
+#ifdef GLARE_ATTN_STAMPS
+  unsigned long long* stamps;   // [n_blocks][4 waves][ATTN_STAMPS]: clock stamps of one tile (tools/attn_stamps.py); nothing reads it.
+                                // The launcher takes it from the workspace argument when key_splits == 1.
+#endif
 };
+
+#ifdef GLARE_ATTN_STAMPS
+// Diagnostic build only (tools/attn_stamps.py; no default build defines GLARE_ATTN_STAMPS): attn_kv_fwd_kernel reads the clock at the
+// phase boundaries of ONE tile per workgroup -- 0 loop top, 1 after the wait + barrier, 2 after K.Q^T, 3 after the softmax, 4 after
+// P.V, 5 the next tile's loop top -- and every wave leaves its six values in p.stamps.  Read the SHARES of that build, not its run time.
+constexpr int ATTN_STAMPS = 6;
+__device__ __forceinline__ unsigned long long attn_stamp() {
+  unsigned long long t;
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+  return t;
+}
+#endif
 
 __global__ __launch_bounds__(AT_THREADS, 1) void attn_fwd_kernel(const AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -329,6 +381,16 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_fwd_kernel(const AttnParam
 // d-halves of a 32-lane pass fall into 8 distinct 32-B slots of the 256-B bank row).
 // Everything else (one wave per SIMD, transposed products, lane-local online softmax, deferred rescale, split keys) is the
 // structure of attn_fwd_kernel above.
+//
+// Schedule of one tile, in clock counts per wave stamped at B = 8, N = 16 275 on random-normal data (tools/attn_stamps.py, a diagnostic
+// build; every figure carries one stamp's own cost; profiles/attn_schedule.txt): wait + barrier 280, K.Q^T 1 216, softmax 490, P.V
+// 1 284, loop 220.  The 32 MFMAs of a product occupy the matrix pipe for 1 024.
+//   * The next tile's 8 LDS-DMA pieces, one per K.Q^T group, cost that phase nothing measurable: K.Q^T takes 1 216 with them and 1 212
+//     without.  Moved into the softmax section (ATTN_KV_PLACE) they cost 40 each there (490 -> 816) and the kernel is 1.5 % slower;
+//     4 there and 4 in the first P.V groups: 1.4 % slower.  The placement stays where it was.
+//   * P.V was the phase with the idle matrix pipe (1 588): the 8 transpose reads of the next group were issued in one run between two
+//     groups of MFMAs.  Two reads behind each MFMA (ATTN_KV_PV_INTERLEAVE) put that issue time under the MFMA: 1 284, the launch
+//     3.94 -> 3.83 ms, bit-identical outputs.
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 
@@ -344,6 +406,11 @@ __device__ __forceinline__ void lgkm_wait8(u32x2 (&f)[8]) {   // ties the wait t
   asm volatile("s_waitcnt lgkmcnt(%8)"
                : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7])
                : "i"(N));
+}
+
+template <int N>
+__device__ __forceinline__ void lgkm_wait2(u32x2& a, u32x2& b) {   // the same for the two reads of one A-fragment
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "i"(N));
 }
 
 // PAIR: the output leaves as a hi / lo pair (p.o_lo); its own instantiation so that the plain kernel's register allocation -- the
@@ -425,7 +492,32 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_kv_fwd_kernel(const AttnPa
       }
   }
 
+  // the pieces that ATTN_KV_PLACE gives slot `sc`, and those that follow step `stepc` of the softmax section
+  auto issue_slot = [&](auto sc, int tile, int buf) {
+    constexpr int slot = decltype(sc)::value, first = kv_place_first(slot);
+    static_for<KV_PLACE[slot]>([&](auto kc) { issue_piece(std::integral_constant<int, first + decltype(kc)::value>{}, tile, buf); });
+  };
+  auto issue_softmax_step = [&](auto stepc, int tile, int buf) {
+    constexpr int step = decltype(stepc)::value;
+    constexpr int lo = kv_softmax_pieces_before(step), n = kv_softmax_pieces_before(step + 1) - lo;
+    static_for<n>([&](auto kc) {
+      issue_piece(std::integral_constant<int, kv_place_first(KV_SLOT_SOFTMAX) + lo + decltype(kc)::value>{}, tile, buf);
+    });
+  };
+
+#ifdef GLARE_ATTN_STAMPS
+  unsigned long long st[ATTN_STAMPS] = {0, 0, 0, 0, 0, 0};
+  const int stamp_tile = t_begin + (t_end - t_begin) / 2;
+#define PROF_MARK(i)                                                        \
+  do {                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                      \
+    if (tile == stamp_tile) st[i] = attn_stamp();                           \
+    if ((i) == 0 && tile == stamp_tile + 1) st[ATTN_STAMPS - 1] = attn_stamp(); \
+    __builtin_amdgcn_sched_barrier(0);                                      \
+  } while (0)
+#else
 #define PROF_MARK(i) do {} while (0)
+#endif
   auto tile_body = [&](auto bufc, int tile) {
     constexpr int BUF = decltype(bufc)::value;
     PROF_MARK(0);                                  // loop overhead
@@ -473,7 +565,7 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_kv_fwd_kernel(const AttnPa
     static_for<8>([&](auto gc) {
       constexpr int g = decltype(gc)::value;
       if constexpr (g + 2 < 8) ldk(std::integral_constant<int, g + 2>{}, fr[(g + 2) % 3]);
-      issue_piece(gc, nxt, BUF ^ 1);
+      issue_slot(gc, nxt, BUF ^ 1);
 #pragma unroll
       for (int e = 0; e < 4; ++e) s = mfma_a16_32x32x16(fr[g % 3][e], qf[4 * g + e], s, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
@@ -513,35 +605,59 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_kv_fwd_kernel(const AttnPa
     }
     float psum = 0.f;
     a16x8 pf[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      u32x4 w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float p0 = __builtin_amdgcn_exp2f(s[8 * h + 2 * e] - m_run);
-        const float p1 = __builtin_amdgcn_exp2f(s[8 * h + 2 * e + 1] - m_run);
-        psum += p0 + p1;
-        w[e] = pack_a2(p0, p1);
-      }
-      pf[h] = __builtin_bit_cast(a16x8, w);
-    }
+    u32x4 pw[2];
+    static_for<KV_SOFTMAX_STEPS>([&](auto stepc) {   // step = one packed pair of P; the softmax slot's pieces go between the steps
+      constexpr int step = decltype(stepc)::value, h = step >> 2, e = step & 3;
+      const float p0 = __builtin_amdgcn_exp2f(s[8 * h + 2 * e] - m_run);
+      const float p1 = __builtin_amdgcn_exp2f(s[8 * h + 2 * e + 1] - m_run);
+      psum += p0 + p1;
+      pw[h][e] = pack_a2(p0, p1);
+      issue_softmax_step(stepc, nxt, BUF ^ 1);
+    });
+    pf[0] = __builtin_bit_cast(a16x8, pw[0]);
+    pf[1] = __builtin_bit_cast(a16x8, pw[1]);
     l_run += psum;
+    {
+      // left alone hipcc hoists the softmax slot's pieces to the head of the section, a burst; pin them: 56 / n vector-ALU instructions
+      // (the section has 16 x {sub, exp2, add} + 8 packs), then one piece
+      static_for<KV_PLACE[KV_SLOT_SOFTMAX]>([&](auto) {
+        __builtin_amdgcn_sched_group_barrier(0x002, kv_softmax_valu_per_piece(), 0);
+        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+      });
+    }
     __builtin_amdgcn_sched_barrier(0);
     PROF_MARK(3);                                  // softmax
     // ---- O^T += V^T . P^T  (512 d x 32 queries, contraction over the 32 keys); group g = d-tiles 2g, 2g+1
     static_for<8>([&](auto gc) {
       constexpr int g = decltype(gc)::value;
-      if constexpr (g + 1 < 8) {
-        ldv(std::integral_constant<int, g + 1>{}, vf[(g + 1) & 1]);
-        wait_v(std::integral_constant<int, 8>{}, vf[g & 1]);
-      } else {
-        wait_v(std::integral_constant<int, 0>{}, vf[g & 1]);
-      }
+      issue_slot(std::integral_constant<int, KV_SLOT_SOFTMAX + 1 + g>{}, nxt, BUF ^ 1);   // none in the placement kept
 #define VF_CUR vf[g & 1]
+      if constexpr (KV_PV_INTERLEAVE) {
+        // reads in program order: ... (g, 0..7), (g+1, 0..7).  Before MFMA e of group g the wave has issued all of group g and reads
+        // 0 .. 2e-1 of group g+1, and needs (g, 2e) and (g, 2e+1): 6 newer reads may still be in flight (the last group has no
+        // successor: 6 - 2e).  The two reads of MFMA e of the NEXT group follow the MFMA, in the shadow of its 32 matrix-pipe cycles.
+        static_for<4>([&](auto ec) {
+          constexpr int e = decltype(ec)::value;
+          lgkm_wait2<(g + 1 < 8) ? 6 : 6 - 2 * e>(VF_CUR[2 * e], VF_CUR[2 * e + 1]);
+          o[2 * g + (e >> 1)] = mfma_a16_32x32x16(vfrag(VF_CUR, e), pf[e & 1], o[2 * g + (e >> 1)], 0, 0, 0);
+          if constexpr (g + 1 < 8) {
+            ldv1(std::integral_constant<int, g + 1>{}, std::integral_constant<int, 2 * e>{}, vf[(g + 1) & 1]);
+            ldv1(std::integral_constant<int, g + 1>{}, std::integral_constant<int, 2 * e + 1>{}, vf[(g + 1) & 1]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        });
+      } else {
+        if constexpr (g + 1 < 8) {
+          ldv(std::integral_constant<int, g + 1>{}, vf[(g + 1) & 1]);
+          wait_v(std::integral_constant<int, 8>{}, vf[g & 1]);
+        } else {
+          wait_v(std::integral_constant<int, 0>{}, vf[g & 1]);
+        }
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        o[2 * g + (e >> 1)] = mfma_a16_32x32x16(vfrag(VF_CUR, e), pf[e & 1], o[2 * g + (e >> 1)], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
+        for (int e = 0; e < 4; ++e)
+          o[2 * g + (e >> 1)] = mfma_a16_32x32x16(vfrag(VF_CUR, e), pf[e & 1], o[2 * g + (e >> 1)], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
     });
     PROF_MARK(4);                                  // P.V
   };
@@ -551,6 +667,13 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_kv_fwd_kernel(const AttnPa
     tile_body(std::integral_constant<int, 0>{}, tile);
     if (tile + 1 < t_end) tile_body(std::integral_constant<int, 1>{}, tile + 1);
   }
+#ifdef GLARE_ATTN_STAMPS
+  if (p.stamps && lane == 0) {
+    unsigned long long* sp = p.stamps + ((size_t)blockIdx.x * (AT_THREADS / 64) + wave) * ATTN_STAMPS;
+#pragma unroll
+    for (int i = 0; i < ATTN_STAMPS; ++i) sp[i] = st[i];
+  }
+#endif
 
   // ---- normalise and store O[q][d] (bf16): a lane owns ONE query row, 4 consecutive d per store
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -673,6 +796,14 @@ extern "C" int glare_attention_kv512_pair_bf16(const void* q, int ldq, const voi
   const long long nb = (long long)B * p.n_qblocks * key_splits;
   if (nb > 0x7fffffffLL) return GLARE_ERR_INVALID;
   p.n_blocks = (int)nb;
+#ifdef GLARE_ATTN_STAMPS
+  // diagnostic build: without key splits nothing uses the workspace, so a workspace given all the same receives the stamps
+  p.stamps = nullptr;
+  if (key_splits == 1 && workspace) {
+    if (workspace_bytes < (size_t)p.n_blocks * (AT_THREADS / 64) * ATTN_STAMPS * sizeof(unsigned long long)) return GLARE_ERR_WORKSPACE;
+    p.stamps = static_cast<unsigned long long*>(workspace);
+  }
+#endif
   const size_t lds = (size_t)2 * KCH * 16;   // 64 KB: the double-buffered 32-key tile
   auto kern = (out_lo && key_splits == 1) ? attn_kv_fwd_kernel<true> : attn_kv_fwd_kernel<false>;   // with key splits the combine kernel writes the pair
   if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
