@@ -28,6 +28,28 @@ def load_network(path_or_state, network, strict=True, submodule=None):
     return result
 
 
+def build_nets(stage, train=False, net_g=None, net_vq=None, options=None, device=None):
+    """(netG, net_hq) of a stage ("stage1": the VQGAN prior itself and None) on `device`, in training or eval mode: name-seeded (seeds
+    0 = VQLLFLOWDeformable, 1 = VQModel, 2 = LLFlowVQGAN2), then the checkpoint files net_g / net_vq (reference format) loaded with
+    strict=False as VQLLFLOWD_model.py:53-63 loads them.  options: stage 2's network options (default: glare_amd.fit's)."""
+    from . import modules as M
+    from .fit import default_options
+    from .synthetic import seeded_init_
+
+    net_hq = seeded_init_(M.VQModel().train(train and stage == "stage1"), 1)
+    if net_vq:
+        load_network(net_vq, net_hq, strict=False)
+    if stage == "stage1":
+        return net_hq.to(device), None
+    if stage == "stage2":
+        netG = seeded_init_(M.LLFlowVQGAN2(opt=options or default_options(stage)).train(train), 2)
+    else:
+        netG = seeded_init_(M.VQLLFLOWDeformable().train(train), 0)
+    if net_g:
+        load_network(net_g, netG, strict=False)
+    return netG.to(device), net_hq.to(device)
+
+
 GRAD_SCALER_STATE = {"scale": 65536.0, "growth_factor": 2.0, "backoff_factor": 0.5, "growth_interval": 2000, "_growth_tracker": 0}
 """What an enabled torch.cuda.amp.GradScaler.state_dict() holds at its defaults.  The reference creates `GradScaler()`
 (LLFlow_model.py:120, VQLLFLOWD_model.py:126) and its resume path calls `scaler.load_state_dict(state['scaler'])`, which raises on
@@ -42,10 +64,9 @@ def adam_state_dict(opt):
     state, groups, idx = {}, [], 0
     for g in opt.groups:
         ids, off = [], 0
-        used = getattr(g, "has_grad", None)
         for j, p in enumerate(g.params):
             k = p.numel()
-            if used is None or used[j]:
+            if g.has_grad[j]:
                 state[idx] = {"step": torch.tensor(float(opt.t)), "exp_avg": g.m[off:off + k].view(p.shape).detach().cpu().clone(),
                               "exp_avg_sq": g.v[off:off + k].view(p.shape).detach().cpu().clone()}
             ids.append(idx)
@@ -83,7 +104,7 @@ def save_training_state(path, trainer, epoch, iter_step, schedulers=(), extra=No
     resume_training reads the five keys above by name and ignores any other."""
     state = {"epoch": epoch, "iter": iter_step, "schedulers": [s.state_dict() for s in schedulers],
              "optimizers": [adam_state_dict(trainer.opt)],
-             "scaler": trainer.opt.scaler_state_dict() if hasattr(trainer.opt, "scaler_state_dict") else dict(GRAD_SCALER_STATE)}
+             "scaler": trainer.opt.scaler_state_dict()}
     state.update(extra or {})
     torch.save(state, path)
 
@@ -93,8 +114,7 @@ def resume_training(path_or_state, trainer, schedulers=()):
     assert len(st["optimizers"]) == 1, "Wrong lengths of optimizers"
     assert len(st["schedulers"]) == len(schedulers), "Wrong lengths of schedulers"
     load_adam_state_dict(trainer.opt, st["optimizers"][0])
-    if hasattr(trainer.opt, "load_scaler_state_dict"):
-        trainer.opt.load_scaler_state_dict(st.get("scaler"))
+    trainer.opt.load_scaler_state_dict(st.get("scaler"))
     for s, sd in zip(schedulers, st["schedulers"]):
         s.load_state_dict(sd)
     return st["epoch"], st["iter"]

@@ -335,16 +335,8 @@ def _stack(ims):
 def load_nets(net_g=None, net_vq=None, device=None):
     """The two networks as glare_amd.infer builds them: name-seeded, checkpoints (reference format) loaded with strict=False."""
     from . import checkpoint
-    from . import modules as M
-    from .synthetic import seeded_init_
 
-    netG = seeded_init_(M.VQLLFLOWDeformable().eval(), 0)
-    net_vq_m = seeded_init_(M.VQModel().eval(), 1)
-    if net_g:
-        checkpoint.load_network(net_g, netG, strict=False)
-    if net_vq:
-        checkpoint.load_network(net_vq, net_vq_m, strict=False)
-    return netG.to(device), net_vq_m.to(device)
+    return checkpoint.build_nets("stage3", net_g=net_g, net_vq=net_vq, device=device)
 
 
 def run(inputs, out_dir, netG=None, net_vq=None, precision=None, batch=8, enhance_fn=None, device=None, tile=None, overlap=64,

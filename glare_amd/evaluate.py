@@ -194,18 +194,8 @@ def warm(stage, netG, net_hq, precision=None, device=None):
 def build_nets(stage, net_vq=None, device=None):
     """(netG, net_hq) of the stage as glare_amd.fit builds them, in eval mode: name-seeded, the VQGAN from `net_vq` if given."""
     from . import checkpoint
-    from . import modules as M
-    from .fit import default_options
-    from .synthetic import seeded_init_
 
-    net_hq = seeded_init_(M.VQModel().eval(), 1)
-    if stage == "stage2":
-        netG = seeded_init_(M.LLFlowVQGAN2(opt=default_options(stage)).eval(), 2)
-    else:
-        netG = seeded_init_(M.VQLLFLOWDeformable().eval(), 0)
-    if net_vq:
-        checkpoint.load_network(net_vq, net_hq, strict=False)
-    return netG.to(device), net_hq.to(device)
+    return checkpoint.build_nets(stage, net_vq=net_vq, device=device)
 
 
 def _read_csv_means(path, cols):
@@ -322,17 +312,8 @@ def main(argv=None):
     lpips_net = None
     if args.lpips:
         from . import metrics
-        from .synthetic import seeded_init_
 
-        lpips_net = metrics.LPIPS(net="alex")
-        if args.lpips_weights:
-            lpips_net.load_state_dict(torch.load(args.lpips_weights, map_location="cpu"), strict=False)
-        else:                       # as glare_amd.infer: the column then only exercises the path
-            seeded_init_(lpips_net, 7)
-            with torch.no_grad():
-                for lin in lpips_net.lins:
-                    lin.model[-1].weight.abs_()
-        lpips_net = lpips_net.to(device)
+        lpips_net = metrics.build_lpips_alex(args.lpips_weights, device)
     nets = build_nets(args.stage, args.net_vq, device)
     res = sweep(args.stage, args.run, args.out or os.path.join(args.run, "results-%s" % args.stage), lows, gts, names, nets, args.select,
                 args.precision, max(1, args.batch), lpips_net, args.save_images, device=device)

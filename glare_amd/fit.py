@@ -32,7 +32,7 @@ from collections import Counter
 import numpy as np
 import torch
 
-from . import checkpoint
+from . import checkpoint, train
 
 # confs/train_stage2_LOL.yml / confs/train_stage3_LOL.yml, the keys this driver reads, restated
 _COMMON_TRAIN = {"manual_seed": 10, "weight_decay_G": 0, "beta1": 0.9, "beta2": 0.99, "lr_scheme": "MultiStepLR", "warmup_iter": 10,
@@ -58,8 +58,7 @@ DEFAULTS = {
                "train": dict(_COMMON_TRAIN, lr_G=5e-5, niter=40000),
                "logger": {"print_freq": 5, "save_checkpoint_freq": 500}},
 }
-DISC_KEY = "discriminator"   # --gan: {"optimizer": Adam state dict, "scaler": GradScaler state dict} of the discriminator
-GAN_TERMS = ("g_loss", "d_weight", "d_loss")
+DISC_KEY = train.DISC_KEY    # --gan: {"optimizer": Adam state dict, "scaler": GradScaler state dict} of the discriminator (Stage1Trainer)
 STATE_KEY = "glare_fit"      # the extra key of a `.state` file: RNG states and the place in the epoch (the reference ignores it)
 STEADY_FROM = 20             # the closing summary's ms per step leaves out this many steps
 
@@ -201,7 +200,7 @@ def _sync():
 
 
 def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=None, validate_fn=None, log=None):
-    """The loop.  trainer: `.opt` (FlatAdam) and `.netG`; dataset: `len()` and `.batch(indices)`.  step_fn(gt, lq) -> loss (device
+    """The loop.  trainer: a train.Trainer; dataset: `len()` and `.batch(indices)`.  step_fn(gt, lq) -> loss (device
     tensor, default trainer.step_tensor) and batch_fn(indices) -> (gt, lq) (default dataset.batch) are injectable, as is
     validate_fn(iter) -> dict.  Returns the list of records it logged (one per print_freq, plus the closing summary)."""
     step_fn = step_fn or trainer.step_tensor
@@ -218,9 +217,7 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
     sched = make_schedule(trainer.opt, options)
     set_random_seed(tr["manual_seed"])
     epoch, step, order, done = 0, 0, None, 0
-    gan = getattr(trainer, "discriminator", None) is not None      # stage 1 with --gan: D's weights, optimizer and scaler travel too
-    percep = getattr(trainer, "perceptual", None)                  # the loss network travels in no file; which one it was does
-    percep = None if percep is None else "%s x %g" % (type(percep).__name__, getattr(trainer, "perceptual_weight", 1.0))
+    percep = trainer.objective_tag()                               # the loss network travels in no file; which one it was does
     if resume:
         st = torch.load(resume, map_location="cpu", weights_only=False) if isinstance(resume, str) else resume
         if STATE_KEY in st and st[STATE_KEY].get("perceptual") != percep:
@@ -230,23 +227,16 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
         if STATE_KEY in st:                  # written by this driver: continue the exact index / augmentation sequence
             _set_rng_state(st[STATE_KEY]["rng"])
             order, done = st[STATE_KEY]["epoch_order"], st[STATE_KEY]["batches_done"]
-        if hasattr(trainer, "global_step"):
-            trainer.global_step = step       # what `disc_start` is compared with
-        if gan:
-            assert DISC_KEY in st, "--gan: the .state file carries no discriminator optimizer (it was written without --gan)"
-            checkpoint.load_adam_state_dict(trainer.opt_d, st[DISC_KEY]["optimizer"])
-            trainer.opt_d.load_scaler_state_dict(st[DISC_KEY]["scaler"])
-
-    tag = getattr(trainer, "checkpoint_tag", "G")        # stage 1 writes <iter>_VQ.pth: the file `--net-vq` takes
+        trainer.on_resume(step)
+        trainer.load_extra_state(st)
 
     def save(epoch, step, order, done):
-        checkpoint.save_network(trainer.netG, os.path.join(out_dir, "models", "%d_%s.pth" % (step, tag)))
-        extra = {STATE_KEY: {"rng": _rng_state(), "epoch_order": order, "batches_done": done}}
+        # <iter>_G.pth (stage 1: <iter>_VQ.pth, the file `--net-vq` takes) and whatever further networks the trainer has (--gan: <iter>_D.pth)
+        for tag, net in {trainer.checkpoint_tag: trainer.netG, **trainer.extra_networks()}.items():
+            checkpoint.save_network(net, os.path.join(out_dir, "models", "%d_%s.pth" % (step, tag)))
+        extra = {STATE_KEY: {"rng": _rng_state(), "epoch_order": order, "batches_done": done}, **trainer.extra_state()}
         if percep:   # (a run without the term writes the state it always wrote)
             extra[STATE_KEY]["perceptual"] = percep
-        if gan:      # <iter>_D.pth: taming's NLayerDiscriminator state dict; its Adam and GradScaler state as one more key of the .state file
-            checkpoint.save_network(trainer.discriminator, os.path.join(out_dir, "models", "%d_D.pth" % step))
-            extra[DISC_KEY] = {"optimizer": checkpoint.adam_state_dict(trainer.opt_d), "scaler": trainer.opt_d.scaler_state_dict()}
         sched._swap_in_current()
         try:
             checkpoint.save_training_state(os.path.join(out_dir, "training_state", "%d.state" % step), trainer, epoch, step, [sched],
@@ -275,10 +265,7 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
                 now = time.perf_counter()
                 rec = {"epoch": epoch, "iter": step, "lr": lr, "loss": loss, "ms_per_step": 1e3 * (now - t_win) / n_win,
                        "ms_batch": 1e3 * t_batch / n_win}
-                if gan:
-                    rec.update((k, float(trainer.last_terms[k])) for k in GAN_TERMS)
-                if getattr(trainer, "perceptual", None) is not None:
-                    rec["percep_loss"] = float(trainer.last_terms["percep_loss"])
+                rec.update((k, float(trainer.last_terms[k])) for k in trainer.log_terms())
             if step - first == STEADY_FROM:
                 _sync()
                 t_steady = time.perf_counter()
@@ -335,23 +322,16 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
     files of the perceptual term (stage 1: LPIPS, both files; stage 3: the VGG16-feature loss, the backbone alone); perceptual_weight:
     stage 1's factor on it (default 1.0).  The loss network is frozen and is written to no checkpoint: a resumed run names the files again."""
     from . import modules as M
-    from .synthetic import seeded_init_
-    from .train import Stage1Trainer, Stage2Trainer, Stage3Trainer
 
     check_perceptual_options(stage, vgg16, lpips_heads, perceptual_weight)
     tr = options["train"]
-    perceptual = build_perceptual(stage, device, vgg16, lpips_heads)
-    extra = {}
-    if perceptual is not None:         # (without the options the trainers are built exactly as before)
-        extra = dict(perceptual=perceptual)
-        if stage == "stage1":
-            extra["perceptual_weight"] = 1.0 if perceptual_weight is None else float(perceptual_weight)
+    perceptual = build_perceptual(stage, device, vgg16, lpips_heads)       # None without the options: the trainers' own default
+    if stage == "stage1" and graph:
+        raise ValueError(GRAPH_REFUSAL)
+    if stage != "stage1" and gan:
+        raise ValueError(GAN_REFUSAL)
+    netG, net_hq = checkpoint.build_nets(stage, True, net_g, net_vq, options, device)
     if stage == "stage1":
-        if graph:
-            raise ValueError(GRAPH_REFUSAL)
-        net = seeded_init_(M.VQModel().train(), 1)
-        if net_vq:
-            checkpoint.load_network(net_vq, net, strict=False)
         disc = None
         if gan:
             set_random_seed(tr["manual_seed"])       # N(0, 0.02) / N(1, 0.02): the same discriminator for the same seed
@@ -359,27 +339,16 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
             if net_d:
                 checkpoint.load_network(net_d, disc, strict=True)
             disc = disc.to(device)
-        return Stage1Trainer(net.to(device), lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0),
-                             codebook_weight=tr.get("codebook_weight", 1.0), precision=precision, discriminator=disc,
-                             disc_start=tr.get("disc_start", 10000), disc_weight=tr.get("disc_weight", 0.8),
-                             disc_factor=tr.get("disc_factor", 1.0), **extra)
-    if gan:
-        raise ValueError(GAN_REFUSAL)
-    net_hq = seeded_init_(M.VQModel().eval(), 1)
+        return train.Stage1Trainer(netG, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0),
+                                   codebook_weight=tr.get("codebook_weight", 1.0), precision=precision, discriminator=disc,
+                                   disc_start=tr.get("disc_start", 10000), disc_weight=tr.get("disc_weight", 0.8),
+                                   disc_factor=tr.get("disc_factor", 1.0), perceptual=perceptual,
+                                   perceptual_weight=1.0 if perceptual_weight is None else float(perceptual_weight))
     if stage == "stage2":
-        netG = seeded_init_(M.LLFlowVQGAN2(opt=options).train(), 2)
-    else:
-        netG = seeded_init_(M.VQLLFLOWDeformable().train(), 0)
-    if net_g:
-        checkpoint.load_network(net_g, netG, strict=False)           # VQLLFLOWD_model.py:53-63 loads with strict=False
-    if net_vq:
-        checkpoint.load_network(net_vq, net_hq, strict=False)
-    netG, net_hq = netG.to(device), net_hq.to(device)
-    if stage == "stage2":
-        return Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
-                             train_rrdb=bool(options["network_G"].get("train_RRDB", False)), device_state=graph, precision=precision)
-    return Stage3Trainer(netG, net_hq, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0), device_state=graph, precision=precision,
-                         **extra)
+        return train.Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
+                                   train_rrdb=bool(options["network_G"].get("train_RRDB", False)), precision=precision)
+    return train.Stage3Trainer(netG, net_hq, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0), precision=precision,
+                               perceptual=perceptual)
 
 
 GAN_REFUSAL = "--gan is a stage1 option: the patch discriminator belongs to the VQGAN prior's objective (stages 2 and 3 train no GAN term)"
@@ -396,8 +365,6 @@ GRAPH_REFUSAL = "--graph is not available for stage1: its step is not captured i
 def graphed_fns(trainer, dataset):
     """(step_fn, batch_fn) that replay the step from a hipGraph: the GraphedStep is built on the first batch (after any resume, as
     its capture_all() asks), and from then on batch() writes straight into its static inputs."""
-    from .train import GraphedStep
-
     box = []
 
     def batch_fn(indices):
@@ -405,7 +372,7 @@ def graphed_fns(trainer, dataset):
 
     def step_fn(gt, lq):
         if not box:
-            box.append(GraphedStep(trainer, gt, lq))
+            box.append(train.GraphedStep(trainer, gt, lq))
         g = box[0]
         return g.step_tensor(g.gt, g.lr)
 

@@ -18,8 +18,7 @@ import numpy as np
 import torch
 
 from . import harness, parallel
-from . import modules as M
-from .synthetic import seeded_init_, synthetic_gt, synthetic_lowlight
+from .synthetic import synthetic_gt, synthetic_lowlight
 
 
 def enhance_batch(netG, net_vq, imgs_u8, device, precision=None):
@@ -60,11 +59,7 @@ def run(n_images, batch=8, h=400, w=600, seed=1234, root=None, net_g=None, net_v
 
     rank, world, device = parallel.init_from_env()
     assert device.type == "cuda", "glare_amd.infer needs an MI355X: the HIP kernels are the only implementation"
-    if nets is not None:
-        netG, net_vq_m = nets
-    else:
-        netG = seeded_init_(M.VQLLFLOWDeformable().eval(), 0)
-        net_vq_m = seeded_init_(M.VQModel().eval(), 1)
+    netG, net_vq_m = nets if nets is not None else checkpoint.build_nets("stage3")
     if net_g:
         checkpoint.load_network(net_g, netG, strict=False)       # VQLLFLOWD_model.py:53-63 loads with strict=False
     if net_vq:
@@ -74,15 +69,7 @@ def run(n_images, batch=8, h=400, w=600, seed=1234, root=None, net_g=None, net_v
     if with_lpips:
         from . import metrics
 
-        lpips_net = metrics.LPIPS(net="alex")
-        if lpips_weights:
-            lpips_net.load_state_dict(torch.load(lpips_weights, map_location="cpu"), strict=False)   # the package's own files hold the heads only
-        else:
-            seeded_init_(lpips_net, 7)
-            with torch.no_grad():
-                for lin in lpips_net.lins:                  # the package's trained heads are non-negative: keep the stand-in a valid distance
-                    lin.model[-1].weight.abs_()
-        lpips_net = lpips_net.to(device)
+        lpips_net = metrics.build_lpips_alex(lpips_weights, device)
     ncols = 1 + int(with_ssim) + int(with_lpips)          # metric columns; one more (the overflow flag) rides along inside this function
     if pairs is not None:
         lows, gts = pairs

@@ -143,6 +143,22 @@ class LPIPS(HipModule):
         return total.float().view(B, 1, 1, 1)
 
 
+def build_lpips_alex(weights=None, device=None):
+    """The LPIPS-alex metric net on `device`: from `weights`, a state dict saved from `lpips.LPIPS(net='alex')`, or -- its AlexNet and
+    linear heads cannot be downloaded here -- name-seeded, so that the column only exercises the path."""
+    from .synthetic import seeded_init_
+
+    net = LPIPS(net="alex")
+    if weights:
+        net.load_state_dict(torch.load(weights, map_location="cpu"), strict=False)   # the package's own files hold the heads only
+    else:
+        seeded_init_(net, 7)
+        with torch.no_grad():
+            for lin in net.lins:                  # the package's trained heads are non-negative: keep the stand-in a valid distance
+                lin.model[-1].weight.abs_()
+    return net.to(device)
+
+
 def to_lpips_input(imgs_u8):
     """Measure.t (Measure.py:48-64): uint8 HWC image(s) on the device -> fp32 NCHW in [-1, 1] (x / 127.5 - 1)."""
     if imgs_u8.dim() == 3:

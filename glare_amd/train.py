@@ -17,8 +17,10 @@ gather through GPU 0 (LLFlow_model.py:72-75).
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import autograd as A
+from . import checkpoint, losses, ops
 from . import train_ops as T
+from .modules import encoder_decoder as ED
 
 
 class FlatGroup:
@@ -41,6 +43,7 @@ class FlatGroup:
         self.g = torch.zeros_like(self.w)
         self.m = torch.zeros_like(self.w)
         self.v = torch.zeros_like(self.w)
+        self._early = None          # the armed early all-reduce of the step in progress (arm_early_all_reduce)
         off = 0
         for p in self.params:
             k = p.numel()
@@ -107,9 +110,13 @@ class FlatGroup:
             off += n
         if grads is not None:     # inside the backward pass: AccumulateGrad has yet to run for these parameters, and a .grad that
             return                # aliases the flat buffer would be accumulated INTO, under the exchange (finish_early_all_reduce re-points)
+        self._expose_grads()
+
+    def _expose_grads(self):
+        """.grad of every parameter = its view of the flat gradient buffer; parameters the graph never reaches keep None, as in torch."""
         off = 0
-        for p, used in zip(self.params, self.has_grad):   # expose the gathered gradient as .grad (a view of the flat buffer);
-            k = p.numel()                                  # parameters the graph never reaches keep .grad = None, as in torch
+        for p, used in zip(self.params, self.has_grad):
+            k = p.numel()
             p.grad = self.g[off:off + k].view(p.shape) if used else None
             off += k
 
@@ -120,7 +127,7 @@ class FlatGroup:
         all-reduce over xGMI.  The reference reduces everything through GPU 0 after backward (nn.DataParallel, LLFlow_model.py:
         71-74).  Call before `loss.backward()`; FlatAdam.step() picks the result up (and falls back to the blocking path if the
         hook never fired).  No-op at world size 1, so the single-GPU step and its hipGraph capture are untouched."""
-        stale, self._early = getattr(self, "_early", None), None
+        stale, self._early = self._early, None
         if stale is not None:          # a backward that raised between arm and step(): its hook must not fire on a later backward
             stale["handle"].remove()   # (a stray collect + all_reduce would desynchronise the ranks' collective order; ADVICE r04)
         if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1) or not self.params:
@@ -140,7 +147,7 @@ class FlatGroup:
     def finish_early_all_reduce(self):
         """-> the world size if the early exchange ran (the flat gradient buffer then holds the all-reduced sum and every .grad is
         its view), else None (nothing armed, or the hook did not fire: the caller collects and reduces as usual)."""
-        state, self._early = getattr(self, "_early", None), None
+        state, self._early = self._early, None
         if state is None:
             return None
         state["handle"].remove()
@@ -149,14 +156,10 @@ class FlatGroup:
         work = state["work"]
         if work is not None and not isinstance(work, int):
             work.wait()
-        off = 0
         for i, (p, used) in enumerate(zip(self.params, self.has_grad)):   # collect()'s check, which the hook's id-keyed dict cannot make:
             if not used and p.grad is not None:                            # a never_used parameter must not have received a gradient
                 raise RuntimeError("a parameter declared never_used received a gradient (index %d, shape %s)" % (i, tuple(p.shape)))
-        for p, used in zip(self.params, self.has_grad):   # AccumulateGrad has since stored the LOCAL gradient tensors in .grad
-            k = p.numel()
-            p.grad = self.g[off:off + k].view(p.shape) if used else None
-            off += k
+        self._expose_grads()                              # AccumulateGrad has since stored the LOCAL gradient tensors in .grad
         return dist.get_world_size()
 
     def all_reduce(self, async_op=False):
@@ -177,15 +180,13 @@ class FlatGroup:
 class FlatAdam:
     """torch.optim.Adam over flat groups with ALL optimizer state on the device -- step count, bias corrections, an lr multiplier,
     GradScaler's found_inf / scale / growth tracker: a step has no host-side state and no host synchronisation (the Python launch
-    loop runs ahead of the GPU; the whole step replays from a hipGraph, GraphedStep).  `device_state` is accepted for
-    compatibility with round 2's two modes; the host-state mode is gone (its inf / NaN check would have cost a sync per step)."""
+    loop runs ahead of the GPU; the whole step replays from a hipGraph, GraphedStep).  `device_state` is accepted and ignored (Trainer)."""
 
     def __init__(self, groups, betas=(0.9, 0.999), eps=1e-8, device_state=True, loss_scaling=False):
         """loss_scaling: fp16 training -- `scale_loss()` multiplies the loss by the scale before backward and step() divides it out
         of the gradients (scaler.scale / scaler.unscale_, LLFlow_model.py:236-241); bf16 training keeps fp32's range and only runs
         the scaler's bookkeeping."""
         self.groups, self.betas, self.eps = groups, betas, eps
-        self.device_state = True
         self.loss_scaling = bool(loss_scaling)
         dev = next(g.w.device for g in groups if g.w.numel())
         # GradScaler's state (torch.cuda.amp.GradScaler defaults, LLFlow_model.py:120): found_inf of the step in progress, the
@@ -272,48 +273,144 @@ STAGE3_NEVER_USED = ("deformable_decoder.scale.", "deformable_decoder.bias.", "d
 STAGE1_NEVER_USED = ("conv_semantic.",)
 
 
-class Stage2Trainer:
+DISC_KEY = "discriminator"   # stage 1 with a discriminator: its Adam and GradScaler state dicts, one more top-level key of a `.state` file
+GAN_TERMS = ("g_loss", "d_weight", "d_loss")
+
+
+def two_group_adam(params, lr, weight_decay, never_used=(), second=(), second_lr=None, second_weight_decay=0.0, betas=(0.9, 0.999),
+                   precision="fp16"):
+    """FlatAdam in the layout of the reference's optimizer: always the two groups [other, RRDB] (LLFlow_model.py:110-118,
+    VQLLFLOWD_model.py:113-121).  The second group is EMPTY wherever the conditional encoder is not trained (stage 2 with train_RRDB:
+    false / before train_RRDB_delay, stage 3, and stage 1 and its discriminator, which have no such encoder), exactly as in the
+    reference's optimizer -- so `.state` files are interchangeable (glare_amd/checkpoint.py).  fp16 scales the loss."""
+    return FlatAdam([FlatGroup(params, lr, weight_decay, never_used=never_used),
+                     FlatGroup(second, lr if second_lr is None else second_lr, second_weight_decay, device=params[0].device)],
+                    betas=betas, loss_scaling=precision == "fp16")
+
+
+def _frozen(net):
+    for p in net.parameters():
+        p.requires_grad_(False)
+    return net.eval()
+
+
+class Trainer:
+    """What the three stages' trainers share, and the ONE interface everything around a trainer talks to (glare_amd.fit, GraphedStep,
+    glare_amd.checkpoint): a new stage or objective term overrides members here instead of being recognised by its callers.
+
+    A trainer has `.netG` (the network it trains and the file <iter>_<checkpoint_tag>.pth holds), `.opt` (its FlatAdam), `.pack_cache`,
+    `.precision` and `.last_terms` (the terms of the last step's loss, device tensors).  `step_tensor(gt, lq=None, branch=None)` is the step
+    without any host synchronisation and returns the loss as a device tensor; `step()` is its float.
+
+    precision: the 16-bit format of activations and activation gradients.  "fp16" (the default) is the reference's own AMP form
+    (`@autocast()` forward + `scaler.scale(loss).backward()`, LLFlowVQGAN_arch.py:36, LLFlow_model.py:236-241): IEEE-half
+    activations, the loss multiplied by the device-resident GradScaler scale, and the precision every gradient-parity bound of
+    tests/test_gpu_train.py is stated in.  "bf16" (fp32 range, no loss scaling, ~1 % faster) rounds every stored tensor 8x
+    coarser and carries NO gradient-parity claim (AFT decoder on the pipeline's inputs: 8 % median / 32 % max against fp16's
+    2 % / 5 %).
+
+    The subclasses' `device_state=` keyword is accepted and ignored: the optimizer's state lives on the device in every mode (the
+    host-state mode it once selected would have cost a synchronisation per step)."""
+
+    checkpoint_tag = "G"                          # glare_amd.fit: <out>/models/<iter>_G.pth
+    perceptual, perceptual_weight = None, 1.0     # the frozen loss network of an objective with a perceptual term, and its factor
+
+    def __init__(self, netG, packed, precision, params, lr, weight_decay, **adam):
+        """packed: the parameters whose packed filters live across steps; params, lr, weight_decay, **adam: two_group_adam's."""
+        assert precision in ("bf16", "fp16")
+        self.precision, self.netG, self.last_terms = precision, netG, {}
+        self.opt = two_group_adam(params, lr, weight_decay, precision=precision, **adam)
+        self.pack_cache = ops.PackCache(packed)
+
+    def step_tensor(self, gt_img, lr_img=None, branch=None):
+        """gt_img: fp32 NCHW ground-truth crop in [0, 1]; lr_img: fp32 NCHW low-light crop (log domain); branch: a key of
+        graph_branches(), None = draw_branch()."""
+        raise NotImplementedError
+
+    def step(self, *args, **kwargs):
+        """step_tensor() with the loss read back: one host synchronisation."""
+        return float(self.step_tensor(*args, **kwargs))
+
+    # ---- what the training driver asks (glare_amd.fit) ----
+    def extra_networks(self):
+        """{suffix: module}: further networks of a checkpoint, written as <iter>_<suffix>.pth beside <iter>_<checkpoint_tag>.pth."""
+        return {}
+
+    def extra_state(self):
+        """Further top-level entries of a `.state` file (the reference's resume reads its five keys by name and ignores any other)."""
+        return {}
+
+    def load_extra_state(self, state):
+        """The resume side of extra_state(): `state` is the whole `.state` dict."""
+
+    def objective_tag(self):
+        """None, or a string naming the part of the objective that travels in no checkpoint (the frozen loss network and its factor): the
+        `.state` file records it, and a resume under another one is refused."""
+        return None if self.perceptual is None else "%s x %g" % (type(self.perceptual).__name__, self.perceptual_weight)
+
+    def on_resume(self, step):
+        """Called with the step count of the `.state` file a run resumes from."""
+
+    def log_terms(self):
+        """The keys of `last_terms` a log record carries beside the loss."""
+        return () if self.perceptual is None else ("percep_loss",)
+
+    # ---- what the graph capture asks (GraphedStep) ----
+    def graph_branches(self):
+        """The keys of every kernel sequence the step can take: a capture covers them all up front.  One for a step without a host-side
+        decision."""
+        return (False,)
+
+    def draw_branch(self):
+        """The step's host-side random decision: the key of graph_branches() this step takes."""
+        return False
+
+    def init_forward(self, gt_img, lr_img, branch):
+        """Whatever data-dependent initialisation the FIRST training forward performs, on its own: no tape kept, nothing updated."""
+
+    def invalidate(self):
+        """Drops the packed inference weights that a step made stale."""
+        self.netG.invalidate()
+
+
+class Stage2Trainer(Trainer):
     """One optimisation step of the flow objective: a7 (frozen VQGAN encoder, no tape) -> a1 -> a4 -> mean NLL -> backward ->
     gradient mean over ranks -> Adam."""
 
     def __init__(self, netG, net_hq, lr_G=5e-4, lr_RRDB=None, weight_decay_G=0.0, train_rrdb=True, device_state=False, precision="fp16"):
-        """precision: the 16-bit format of activations and activation gradients.  "fp16" (the default) is the reference's own AMP form
-        (`@autocast()` forward + `scaler.scale(loss).backward()`, LLFlowVQGAN_arch.py:36, LLFlow_model.py:236-241): IEEE-half
-        activations, the loss multiplied by the device-resident GradScaler scale, and the precision every gradient-parity bound of
-        tests/test_gpu_train.py is stated in.  "bf16" (fp32 range, no loss scaling, ~1 % faster) rounds every stored tensor 8x
-        coarser and carries NO gradient-parity claim (AFT decoder on the pipeline's inputs: 8 % median / 32 % max against fp16's
-        2 % / 5 %)."""
-        assert precision in ("bf16", "fp16")
-        self.precision = precision
-        self.netG, self.net_hq = netG.train(), net_hq.eval()
-        for p in net_hq.parameters():
-            p.requires_grad_(False)
+        self.net_hq = _frozen(net_hq)
         rrdb = [p for n, p in netG.named_parameters() if n.startswith("RRDB.")]
         other = [p for n, p in netG.named_parameters() if not n.startswith("RRDB.")]
         if not train_rrdb:  # train_RRDB_delay (LLFlow_model.py:142-150): the encoder joins after a fraction of the run
             for p in rrdb:
                 p.requires_grad_(False)
-        # always the reference's two groups [other, RRDB] (LLFlow_model.py:110-118); the RRDB group is EMPTY while the
-        # conditional encoder is frozen (train_RRDB: false / before train_RRDB_delay), exactly as in the reference's
-        # optimizer -- so `.state` files are interchangeable (glare_amd/checkpoint.py)
         never = [p for n, p in netG.named_parameters() if n.startswith(STAGE2_NEVER_USED)]
-        self.opt = FlatAdam([FlatGroup(other, lr_G, weight_decay_G, never_used=never),
-                             FlatGroup(rrdb if train_rrdb else [], lr_G if lr_RRDB is None else lr_RRDB, 1e-5,
-                                       device=other[0].device)], device_state=device_state, loss_scaling=precision == "fp16")
-        self.pack_cache = ops.PackCache([p for p in netG.parameters() if p.requires_grad])   # packed filters live across steps
+        super().__init__(netG.train(), [p for p in netG.parameters() if p.requires_grad], precision, other, lr_G, weight_decay_G,
+                         never_used=never, second=rrdb if train_rrdb else [], second_lr=lr_RRDB, second_weight_decay=1e-5)
+
+    def graph_branches(self):
+        """mean = color_map, and mean = gt where it can be drawn (train_gt_ratio > 0: 0.2 in confs/train_stage2_LOL.yml, 0 in LOL.yml)."""
+        return (False, True) if float(self.netG.train_gt_ratio) > 0.0 else (False,)
 
     def draw_branch(self):
         """The step's one host-side random decision (LLFlowVQGAN_arch.py:95): is the Gaussian's mean the ground truth?"""
         return self.netG._mean_is_gt(None)
 
-    def step(self, gt_img, lr_img, mean_is_gt=None):
-        """gt_img: fp32 NCHW ground-truth crop in [0,1]; lr_img: fp32 NCHW low-light crop (log domain).  Returns the loss."""
-        return float(self.step_tensor(gt_img, lr_img, mean_is_gt))
+    def init_forward(self, gt_img, lr_img, branch):
+        """The forward half of a step only (what initialises a fresh flow's ActNorms)."""
+        flow = self.netG.flowUpsamplerNet
+        with ops.use_precision(self.precision), torch.no_grad():
+            if flow.needs_actnorm_init():                      # exactly what train_nll() does first (LLFlowVQGAN_arch.train_nll)
+                with ops.auto_cout_tile():
+                    gt_latent = self.net_hq.encode_nhwc(gt_img)
+                enc0 = self.netG.RRDB.forward_nhwc(lr_img)
+                flow.initialize_actnorms_nhwc(gt_latent.detach(), enc0["cond_feat"])
 
-    def step_tensor(self, gt_img, lr_img, mean_is_gt=None):
-        """The step without any host synchronisation: returns the loss as a device tensor.  mean_is_gt: None = draw with
-        probability train_gt_ratio as the reference does; True / False = forced (GraphedStep draws before choosing a graph)."""
-        flag = self.draw_branch() if mean_is_gt is None else bool(mean_is_gt)
+    def step_tensor(self, gt_img, lr_img=None, branch=None, *, mean_is_gt=None):
+        """branch (or, by keyword, mean_is_gt): None = draw with probability train_gt_ratio as the reference does; True / False =
+        forced (GraphedStep draws before choosing a graph)."""
+        branch = mean_is_gt if branch is None else branch
+        flag = self.draw_branch() if branch is None else bool(branch)
         with ops.use_precision(self.precision):
             with torch.no_grad(), ops.auto_cout_tile():
                 gt_latent = self.net_hq.encode_nhwc(gt_img)            # LLFlow_model.py:200-201
@@ -324,11 +421,11 @@ class Stage2Trainer:
                 self.opt.groups[0].arm_early_all_reduce()              # N > 1: the flow group's all-reduce runs under the encoder's backward
                 self.opt.scale_loss(loss).backward()                   # :236  scaler.scale(loss).backward()
             self.opt.step()                                            # :240-241  scaler.step(); scaler.update()
-        self.netG.invalidate()                                     # packed inference weights are stale now
+        self.invalidate()                                          # packed inference weights are stale now
         return loss.detach()
 
 
-class Stage3Trainer:
+class Stage3Trainer(Trainer):
     """One optimisation step of stage 3 (row a13, VQLLFLOWDModel.optimize_parameters, VQLLFLOWD_model.py:187-232): the
     conditional encoder, the flow (reverse) and the VQGAN decoder run without a tape exactly as in inference
     (VQLLFLOWDeformable_arch.py:231-248); only `deformable_decoder` is trained.  Loss (:217-223): L1 + 0.01 * VGG16-feature
@@ -337,42 +434,26 @@ class Stage3Trainer:
 
     def __init__(self, netG, net_hq, lr_G=5e-5, weight_decay_G=0.0, perceptual=None, use_msssim=True, device_state=False, precision="fp16",
                  frozen_fp32_class=False):
-        """precision: as Stage2Trainer ("fp16" = the reference's AMP form, the default).  frozen_fp32_class: run the FROZEN conditional
-        encoder + flow in the fp32-class inference form (hi / lo operand pairs, three MFMA passes per conv) instead of the single-pass
-        fp16 form.  Default False: the reference runs these nets under `@autocast()` in the stage-3 step (VQLLFLOWDeformable_arch.py:
-        222-248), i.e. single-pass fp16 is ITS arithmetic; the fp32-class form serves inference's index contract and costs the step
-        ~3.5 ms (23.0 -> 19.5 ms at 1 x 256^2, round 4 / 5)."""
-        from . import autograd as A
-        from . import losses
-        from .modules import encoder_decoder as ED
-
-        assert precision in ("bf16", "fp16")      # as Stage2Trainer
-        self.precision = precision
-        self._front = lambda: ED.fp32_class(bool(frozen_fp32_class))
-
-        self.A, self.losses, self.perceptual, self.use_msssim = A, losses, perceptual, use_msssim
-        self.last_terms = {}
-        self.netG, self.net_hq = netG, net_hq.eval()
-        for p in net_hq.parameters():
-            p.requires_grad_(False)
+        """frozen_fp32_class: run the FROZEN conditional encoder + flow in the fp32-class inference form (hi / lo operand pairs, three
+        MFMA passes per conv) instead of the single-pass fp16 form.  Default False: the reference runs these nets under `@autocast()`
+        in the stage-3 step (VQLLFLOWDeformable_arch.py:222-248), i.e. single-pass fp16 is ITS arithmetic; the fp32-class form serves
+        inference's index contract and costs the step ~3.5 ms (23.0 -> 19.5 ms at 1 x 256^2, round 4 / 5)."""
+        self.frozen_fp32_class, self.perceptual, self.use_msssim = bool(frozen_fp32_class), perceptual, use_msssim
+        self.net_hq = _frozen(net_hq)
         for n, p in netG.named_parameters():
             p.requires_grad_(n.startswith("deformable_decoder."))
         dd = [p for n, p in netG.named_parameters() if n.startswith("deformable_decoder.")]
-        # the reference's optimizer always has the two groups [other, RRDB] (VQLLFLOWD_model.py:113-121); at stage 3 the
-        # conditional encoder is frozen (fix_modules), so its group is empty -- kept for `.state` file compatibility
         never = [p for n, p in netG.named_parameters() if n.startswith(STAGE3_NEVER_USED)]
-        self.opt = FlatAdam([FlatGroup(dd, lr_G, weight_decay_G, never_used=never), FlatGroup([], lr_G, 1e-5, device=dd[0].device)],
-                            device_state=device_state, loss_scaling=precision == "fp16")
-        self.pack_cache = ops.PackCache(dd)
+        super().__init__(netG, dd, precision, dd, lr_G, weight_decay_G, never_used=never, second_weight_decay=1e-5)
 
-    def step(self, gt_img, lr_img):
-        """gt_img: fp32 NCHW in [0,1]; lr_img: fp32 NCHW low-light crop (log domain).  Returns the loss."""
-        return float(self.step_tensor(gt_img, lr_img))
+    def invalidate(self):
+        """Only the deformable decoder's packed inference weights go stale; the frozen nets keep theirs."""
+        self.netG.deformable_decoder.invalidate()
 
-    def step_tensor(self, gt_img, lr_img):
+    def step_tensor(self, gt_img, lr_img=None, branch=None):
         G = self.netG
         with ops.use_precision(self.precision):
-            with torch.no_grad(), ops.auto_cout_tile(), self._front():
+            with torch.no_grad(), ops.auto_cout_tile(), ED.fp32_class(self.frozen_fp32_class):
                 enc = G.RRDB.forward_nhwc(lr_img)
                 lat = G.flowUpsamplerNet.decode_nhwc(enc["color_map"], enc["cond_feat"])
                 _, _, feats = self.net_hq.decode_nhwc(lat, want_image=False)
@@ -382,11 +463,11 @@ class Stage3Trainer:
                 loss, self.last_terms = stage3_loss(rec, gt_img, self.perceptual, self.use_msssim)
                 self.opt.scale_loss(loss).backward()
             self.opt.step()
-        G.deformable_decoder.invalidate()   # only its packed inference weights went stale; the frozen nets keep theirs
+        self.invalidate()
         return loss.detach()
 
 
-class Stage1Trainer:
+class Stage1Trainer(Trainer):
     """One optimisation step of stage 1, the VQGAN prior itself (VQModel.forward + configure_optimizers, VQModel_arch.py:98-101,
     148-157): x -> encoder -> quant_conv -> codebook (straight-through) -> post_quant_conv -> decoder, every layer with a tape.
     Loss: mean |xrec - x| + codebook_weight * qloss (+ perceptual_weight * perceptual(xrec, x) when a perceptual network is passed).
@@ -410,51 +491,65 @@ class Stage1Trainer:
     is launched and the generator's update is today's, bit for bit.  The optimizer is the reference's: Adam, betas (0.5, 0.9), one group
     over encoder, decoder, quantize, quant_conv and post_quant_conv (:148-157)."""
 
+    checkpoint_tag = "VQ"                            # glare_amd.fit: <out>/models/<iter>_VQ.pth, the file `--net-vq` takes
+
     def __init__(self, net, lr_G=1e-4, weight_decay_G=0.0, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0,
                  device_state=False, precision="fp16", discriminator=None, disc_start=10000, disc_weight=0.8, disc_factor=1.0):
         """lr_G: a starting point, not a tuned value (the reference sets `self.learning_rate` from a config it does not ship).
-        precision: as Stage2Trainer ("fp16" = AMP with the device-resident GradScaler, the default; "bf16" on request).
         discriminator: an NLayerDiscriminator on the net's device, or None (no GAN term: the step and every file are what they were);
         disc_start / disc_weight / disc_factor: taming's defaults for the VQGAN configs."""
-        from . import autograd as A
-
-        assert precision in ("bf16", "fp16")
-        self.precision, self.A = precision, A
         self.codebook_weight, self.perceptual, self.perceptual_weight = float(codebook_weight), perceptual, float(perceptual_weight)
-        self.last_terms = {}
-        self.checkpoint_tag = "VQ"                   # glare_amd.fit: <out>/models/<iter>_VQ.pth, the file `--net-vq` takes
-        self.net = self.netG = net.train()           # `netG`: the name the driver and the checkpoint code read
         for p in net.parameters():
             p.requires_grad_(True)
         named = list(net.named_parameters())
         never = [p for n, p in named if n.startswith(STAGE1_NEVER_USED)]
-        # one group, and an empty second one so that `.state` files have the layout of the other stages
-        self.opt = FlatAdam([FlatGroup([p for _, p in named], lr_G, weight_decay_G, never_used=never),
-                             FlatGroup([], lr_G, 0.0, device=named[0][1].device)], betas=(0.5, 0.9), device_state=device_state,
-                            loss_scaling=precision == "fp16")
-        self.pack_cache = ops.PackCache([p for n, p in named if not n.startswith(STAGE1_NEVER_USED)])
+        super().__init__(net.train(), [p for n, p in named if not n.startswith(STAGE1_NEVER_USED)], precision, [p for _, p in named], lr_G,
+                         weight_decay_G, never_used=never, betas=(0.5, 0.9))
+        self.net = self.netG                         # `netG`: the name the driver and the checkpoint code read
         self.discriminator, self.opt_d = discriminator, None
         self.disc_start, self.disc_weight, self.disc_factor = int(disc_start), float(disc_weight), float(disc_factor)
-        self.global_step = 0                         # Lightning's global_step: steps taken so far (the driver restores it on resume)
+        self.global_step = 0                         # Lightning's global_step: steps taken so far (on_resume restores it)
         if discriminator is not None:
             discriminator.train()
             for p in discriminator.parameters():
                 p.requires_grad_(True)
             dparams = list(discriminator.parameters())
-            self.opt_d = FlatAdam([FlatGroup(dparams, lr_G, 0.0), FlatGroup([], lr_G, 0.0, device=dparams[0].device)], betas=(0.5, 0.9),
-                                  device_state=device_state, loss_scaling=precision == "fp16")
+            self.opt_d = two_group_adam(dparams, lr_G, 0.0, betas=(0.5, 0.9), precision=precision)
             self._zero = torch.zeros((), dtype=torch.float32, device=dparams[0].device)
+
+    def extra_networks(self):
+        """<iter>_D.pth: taming's NLayerDiscriminator state dict."""
+        return {} if self.discriminator is None else {"D": self.discriminator}
+
+    def extra_state(self):
+        """D's Adam and GradScaler state travel as one more key of the `.state` file."""
+        if self.discriminator is None:
+            return {}
+        return {DISC_KEY: {"optimizer": checkpoint.adam_state_dict(self.opt_d), "scaler": self.opt_d.scaler_state_dict()}}
+
+    def load_extra_state(self, state):
+        if self.discriminator is not None:
+            assert DISC_KEY in state, "--gan: the .state file carries no discriminator optimizer (it was written without --gan)"
+            checkpoint.load_adam_state_dict(self.opt_d, state[DISC_KEY]["optimizer"])
+            self.opt_d.load_scaler_state_dict(state[DISC_KEY]["scaler"])
+
+    def on_resume(self, step):
+        self.global_step = step                      # what `disc_start` is compared with
+
+    def log_terms(self):
+        return (GAN_TERMS if self.discriminator is not None else ()) + super().log_terms()
+
+    def invalidate(self):
+        self.net.invalidate()
+        if self.discriminator is not None:
+            self.discriminator.invalidate()
 
     def get_last_layer(self):
         """VQModel.get_last_layer (VQModel_arch.py:159-160): the weight the adaptive GAN weight takes its two gradient norms at."""
         return self.net.decoder.conv_out.weight
 
-    def step(self, gt_img, lr_img=None):
-        """gt_img: fp32 NCHW ground-truth crop in [0, 1]; lr_img is ignored (the driver hands both halves of a pair).  Returns the loss."""
-        return float(self.step_tensor(gt_img, lr_img))
-
-    def step_tensor(self, gt_img, lr_img=None):
-        """The step without any host synchronisation: returns the loss as a device tensor."""
+    def step_tensor(self, gt_img, lr_img=None, branch=None):
+        """lr_img is ignored (the driver hands both halves of a pair)."""
         gt = gt_img.float().contiguous()
         t, self.global_step = self.global_step, self.global_step + 1
         if self.discriminator is not None and t >= self.disc_start and self.disc_factor != 0.0:
@@ -479,7 +574,6 @@ class Stage1Trainer:
         return logits[:B], logits[B:]
 
     def _gan_step(self, gt):
-        A, D = self.A, self.discriminator
         f = self.disc_factor
         with ops.use_precision(self.precision):
             self.opt.zero_grad()
@@ -513,8 +607,7 @@ class Stage1Trainer:
                 torch.autograd.backward(self.opt_d.scale_loss(d_loss), inputs=self.opt_d.groups[0].params)
             self.opt.step()
             self.opt_d.step()
-        self.net.invalidate()
-        D.invalidate()
+        self.invalidate()
         loss = nll.detach() + d_weight * f * g_loss.detach() + cb.detach()
         terms["codebook_loss"] = cb
         terms.update(g_loss=g_loss.detach(), d_weight=d_weight, d_loss=d_loss.detach())
@@ -528,7 +621,7 @@ class Stage1Trainer:
         with ops.use_precision(self.precision):
             self.opt_d.zero_grad()
             logits_real, logits_fake = self._disc_logits(gt, xrec_nhwc.detach().float().contiguous())
-            d_loss = (self.A.hinge_loss(logits_real, "real") + self.A.hinge_loss(logits_fake, "fake")) * (0.5 * self.disc_factor)
+            d_loss = (A.hinge_loss(logits_real, "real") + A.hinge_loss(logits_fake, "fake")) * (0.5 * self.disc_factor)
             self.opt_d.scale_loss(d_loss).backward()
             self.opt_d.step()
         self.discriminator.invalidate()
@@ -539,9 +632,6 @@ class Stage1Trainer:
 def stage1_loss(xrec_nhwc, gt_nchw, qloss, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0):
     """total = mean |xrec - x| + codebook_weight * qloss (+ perceptual_weight * perceptual(xrec, x)) on the NHWC fp32 reconstruction.
     Returns (total, {term: float-able tensor})."""
-    from . import autograd as A
-    from . import ops
-
     terms = {"l1_loss": A.l1_loss(xrec_nhwc, gt_nchw)}
     if qloss is not None:                # None: the reconstruction terms alone (the GAN step's nll)
         terms["codebook_loss"] = qloss * codebook_weight
@@ -553,9 +643,6 @@ def stage1_loss(xrec_nhwc, gt_nchw, qloss, codebook_weight=1.0, perceptual=None,
 def stage3_loss(rec_nhwc, gt_nchw, perceptual=None, use_msssim=True):
     """total = l1 + 0.01 * percep + 0.2 * (1 - msssim(sr, gt, normalize=True)) on the NHWC fp32 network output
     (VQLLFLOWD_model.py:209-223).  Returns (total, {term: float-able tensor})."""
-    from . import autograd as A
-    from . import losses, ops
-
     gt_nchw = gt_nchw.float().contiguous()
     terms = {"l1_loss": A.l1_clamp_loss(rec_nhwc, gt_nchw)}
     if perceptual is not None or use_msssim:
@@ -570,17 +657,15 @@ def stage3_loss(rec_nhwc, gt_nchw, perceptual=None, use_msssim=True):
 
 class GraphedStep:
     """A training step captured once into a hipGraph (torch.cuda.CUDAGraph) and replayed: the ~5 000 kernel launches of a step
-    at the reference's crop sizes are launch-bound from Python, the graph removes the host from the loop.  Needs a trainer
-    built with device_state=True (no host-side optimizer state) and fixed input shapes; inputs are copied into static buffers.
-    World size 1 only (a collective inside the captured region is not attempted).
+    at the reference's crop sizes are launch-bound from Python, the graph removes the host from the loop.  Needs fixed input
+    shapes; inputs are copied into static buffers.  World size 1 only (a collective inside the captured region is not attempted).
 
-    A stage-2 step has one host-side random decision (mean = ground truth with probability train_gt_ratio,
-    LLFlowVQGAN_arch.py:95) that changes the captured kernel sequence: the decision is drawn on the host BEFORE the replay
-    and selects one of two graphs, both captured up front (capture_all)."""
+    A step with a host-side decision that changes the captured kernel sequence (stage 2: mean = ground truth with probability
+    train_gt_ratio, LLFlowVQGAN_arch.py:95) has one graph per branch (Trainer.graph_branches), all captured up front (capture_all):
+    the decision is drawn on the host BEFORE the replay (Trainer.draw_branch) and selects the graph."""
 
     def __init__(self, trainer, gt_img, lr_img, warmup=3):
         self.trainer = trainer
-        self.branching = hasattr(trainer, "draw_branch")
         self.gt, self.lr = gt_img.clone(), lr_img.clone()
         self.warmup = warmup
         self.graphs = {}
@@ -592,9 +677,13 @@ class GraphedStep:
         other never touched must have done so BEFORE any graph holds the table), allocator pools, lazily built folds.  Call again
         after `resume_training` / loading weights: the old graphs are dropped."""
         self.graphs = {}
-        # the mean = gt branch exists only when it can be drawn (train_gt_ratio > 0: 0.2 in confs/train_stage2_LOL.yml, 0 in LOL.yml)
-        both = self.branching and float(getattr(self.trainer.netG, "train_gt_ratio", 0.0)) > 0.0
-        flags = (False, True) if both else (False,)
+        branches = self.trainer.graph_branches()
+        self._warm_up(branches)
+        self.trainer.invalidate()
+        for b in branches:
+            self._capture(b)
+
+    def _warm_up(self, branches):
         # The warm-up runs REAL steps (allocator pools, lazy folds, the PackCache's job table must exist before the capture), on the
         # batch cloned at construction: the training state is snapshotted around it and put back, so that capturing -- at construction
         # or again after `resume_training` / a weight load -- never advances the optimisation (ADVICE r03: it used to apply
@@ -615,61 +704,36 @@ class GraphedStep:
                 # its own -- a forward without backward or optimizer step -- and cloned BEFORE any warm-up step: cloned after the warm-up
                 # (as this code did) the values put back were the initialisation PLUS warmup x branches Adam updates on the construction
                 # batch, with their moments and the step counter rewound to zero.
-                self._init_forward(flags[0])
+                self.trainer.init_forward(self.gt, self.lr, branches[0])
                 keep = [(t, t.clone()) for m in actnorms if id(m) in fresh for t in (m.bias.data, m.logs.data)]
             for _ in range(self.warmup):            # allocator / lazy-init warm-up outside the capture, every branch
-                for f in flags:
-                    self._eager(f)
+                for b in branches:
+                    self.trainer.step_tensor(self.gt, self.lr, b)
             for t, v in snap:
                 t.copy_(v)
             for t, v in keep:                       # the parameters live inside the restored flat buffers: put the initialisation back
                 t.copy_(v)
         torch.cuda.current_stream().wait_stream(side)
-        self._invalidate()
-        for f in flags:
-            self._capture(f)
 
-    def _eager(self, flag):
-        return self.trainer.step_tensor(self.gt, self.lr, flag) if self.branching else self.trainer.step_tensor(self.gt, self.lr)
-
-    def _init_forward(self, flag):
-        """The forward half of a stage-2 step only (what initialises a fresh flow's ActNorms), no tape kept, nothing updated."""
-        tr = self.trainer
-        if not isinstance(tr, Stage2Trainer):
-            return
-        flow = tr.netG.flowUpsamplerNet
-        with ops.use_precision(tr.precision), torch.no_grad():
-            if flow.needs_actnorm_init():                      # exactly what train_nll() does first (LLFlowVQGAN_arch.train_nll)
-                with ops.auto_cout_tile():
-                    gt_latent = tr.net_hq.encode_nhwc(self.gt)
-                enc0 = tr.netG.RRDB.forward_nhwc(self.lr)
-                flow.initialize_actnorms_nhwc(gt_latent.detach(), enc0["cond_feat"])
-
-    def _capture(self, flag):
+    def _capture(self, branch):
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            loss = self._eager(flag)
-        self.graphs[flag] = (g, loss)
-        # the capture only RECORDS: it must not advance the optimizer.  (Capturing runs no kernels; the host-side step
-        # counter lives on the device in device_state mode, so nothing to undo.)
-
-    def _invalidate(self):
-        # the host code inside step_tensor (netG.invalidate()) ran at capture time only: packed inference weights built
-        # since then (a validation pass between steps) would be stale after this replay
-        tr = self.trainer
-        (tr.netG.deformable_decoder if isinstance(tr, Stage3Trainer) else tr.netG).invalidate()
+            loss = self.trainer.step_tensor(self.gt, self.lr, branch)
+        self.graphs[branch] = (g, loss)
+        # the capture only RECORDS: it must not advance the optimizer.  (Capturing runs no kernels, and the optimizer's step
+        # counter lives on the device, so nothing to undo.)
 
     def step_tensor(self, gt_img, lr_img, mean_is_gt=None):
-        flag = False
-        if self.branching:
-            flag = self.trainer.draw_branch() if mean_is_gt is None else bool(mean_is_gt)
+        branch = self.trainer.draw_branch() if mean_is_gt is None else bool(mean_is_gt)
         self.gt.copy_(gt_img)
         self.lr.copy_(lr_img)
-        if flag not in self.graphs:      # a forced branch the configuration itself cannot draw (tests): captured on first use --
-            self._capture(flag)          # safe, the PackCache keeps superseded job tables alive for the graphs that hold them
-        g, loss = self.graphs[flag]
+        if branch not in self.graphs:    # a forced branch the configuration itself cannot draw (tests): captured on first use --
+            self._capture(branch)        # safe, the PackCache keeps superseded job tables alive for the graphs that hold them
+        g, loss = self.graphs[branch]
         g.replay()
-        self._invalidate()
+        # the host code inside step_tensor (its invalidate()) ran at capture time only: packed inference weights built since then (a
+        # validation pass between steps) would be stale after this replay
+        self.trainer.invalidate()
         return loss
 
     def step(self, gt_img, lr_img):

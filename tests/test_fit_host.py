@@ -12,7 +12,7 @@ import pytest
 import torch
 from PIL import Image
 
-from glare_amd import checkpoint, fit
+from glare_amd import checkpoint, fit, train
 from glare_amd import data as D
 
 SIZES = [(40, 56), (33, 47), (24, 24), (64, 48), (37, 37), (50, 50)]      # one smaller than the 32-crop, odd sizes, squares
@@ -84,7 +84,15 @@ def _torch_lrs(niter, warmup, rels, gamma, lr0, make):
 def _stub_opt(lr=5e-5):
     scales = []
     groups = [types.SimpleNamespace(params=[], lr=lr, weight_decay=0.0), types.SimpleNamespace(params=[], lr=lr, weight_decay=1e-5)]
-    return types.SimpleNamespace(groups=groups, betas=(0.9, 0.999), eps=1e-8, t=0, set_lr_scale=scales.append, scales=scales)
+    return types.SimpleNamespace(groups=groups, betas=(0.9, 0.999), eps=1e-8, t=0, set_lr_scale=scales.append, scales=scales,
+                                 scaler_state_dict=lambda: dict(checkpoint.GRAD_SCALER_STATE), load_scaler_state_dict=lambda sd: None)
+
+
+class _StubTrainer(train.Trainer):
+    """The least a driver needs, built without a device: an optimizer and a network; every member of the interface at its default."""
+
+    def __init__(self, opt, netG=None):
+        self.opt, self.netG = opt, netG
 
 
 def _options(niter=200, batch=2, save=10, print_freq=5):
@@ -155,10 +163,10 @@ def test_index_order_equals_the_dataloader(n, batch):
 class _Stub:
     """A dataset of 7 'images' whose batch() draws as DeviceLoLDataset does, and a step that consumes Python's `random` as stage 2 does."""
 
-    def __init__(self, tmp):
+    def __init__(self, tmp, trainer=None):
         self.ds = types.SimpleNamespace(pairs=[[np.zeros((40 + i, 50, 3), np.uint8)] * 2 + ["x"] for i in range(7)], use_crop=True, crop_size=32,
                                         center_crop_hr_size=None, use_flip=True, use_rot=True)
-        self.trainer = types.SimpleNamespace(opt=_stub_opt(), netG=torch.nn.Linear(2, 2))
+        self.trainer = trainer or _StubTrainer(_stub_opt(), torch.nn.Linear(2, 2))
         self.trace, self.out = [], str(tmp)
 
     def __len__(self):
@@ -211,6 +219,138 @@ def test_loop_mechanics_checkpoint_cadence_and_exact_resume(tmp_path):
     assert c.trace == a.trace[17:]
 
 
+class _Recorder(_StubTrainer):
+    """Overrides every member of train.Trainer's interface and records the calls."""
+
+    checkpoint_tag = "MAIN"
+
+    def __init__(self, tag="Stub x 2", branches=("a", "b")):
+        super().__init__(_stub_opt(), torch.nn.Linear(2, 2))
+        self.side, self.tag, self.branches, self.calls, self.value = torch.nn.Linear(3, 1), tag, branches, [], 0.0
+        self.next_branch = branches[0]
+
+    def step_tensor(self, gt_img, lr_img=None, branch=None):
+        self.calls.append(("step", branch))
+        self.value += 1.5
+        self.last_terms = {"aux": torch.tensor(self.value), "unlogged": torch.tensor(-1.0)}
+        return torch.tensor(self.value * 2)
+
+    def extra_networks(self):
+        return {"SIDE": self.side}
+
+    def extra_state(self):
+        return {"stub_extra": {"value": self.value}}
+
+    def load_extra_state(self, state):
+        self.calls.append(("load_extra_state", state["stub_extra"]))
+
+    def objective_tag(self):
+        return self.tag
+
+    def on_resume(self, step):
+        self.calls.append(("on_resume", step))
+
+    def log_terms(self):
+        return ("aux",)
+
+    def graph_branches(self):
+        return self.branches
+
+    def draw_branch(self):
+        self.calls.append(("draw_branch",))
+        return self.next_branch
+
+    def init_forward(self, gt_img, lr_img, branch):
+        self.calls.append(("init_forward", branch))
+
+    def invalidate(self):
+        self.calls.append(("invalidate",))
+
+
+def test_driver_asks_the_trainer_and_nothing_else(tmp_path):
+    """The loop's files, `.state` entries, record keys and resume go through train.Trainer's members: (a) the extra network file and
+    the extra `.state` entry appear under the trainer's names and come back through load_extra_state; (b) on_resume gets the resumed
+    step; (c) a resume under another objective_tag() is refused; (d) a trainer that overrides nothing writes what it always wrote."""
+    tr = _Recorder()
+    a = _Stub(tmp_path / "a", tr)
+    opts = _options(niter=30, save=7)
+
+    def stop_at_9(gt, lq):
+        if sum(c[0] == "step" for c in tr.calls) == 9:
+            raise KeyboardInterrupt
+        return tr.step_tensor(gt, lq)
+
+    recs = []
+    with pytest.raises(KeyboardInterrupt):
+        fit.fit(opts, tr, a, a.out, step_fn=stop_at_9, batch_fn=a.batch, log=recs.append)
+    # (a) the names are the trainer's
+    assert sorted(os.listdir(os.path.join(a.out, "models"))) == ["7_MAIN.pth", "7_SIDE.pth"]
+    assert os.listdir(os.path.join(a.out, "training_state")) == ["7.state"]
+    side = torch.load(os.path.join(a.out, "models", "7_SIDE.pth"), map_location="cpu")
+    assert set(side) == set(tr.side.state_dict()) and all(torch.equal(v, tr.side.state_dict()[k]) for k, v in side.items())
+    main = torch.load(os.path.join(a.out, "models", "7_MAIN.pth"), map_location="cpu")
+    assert all(torch.equal(v, tr.netG.state_dict()[k]) for k, v in main.items())
+    st = torch.load(os.path.join(a.out, "training_state", "7.state"), map_location="cpu", weights_only=False)
+    assert set(st) == {"epoch", "iter", "schedulers", "optimizers", "scaler", fit.STATE_KEY, "stub_extra"}
+    assert st["stub_extra"] == {"value": 7 * 1.5} and st[fit.STATE_KEY]["perceptual"] == "Stub x 2"
+    assert set(recs[0]) == {"epoch", "iter", "lr", "loss", "ms_per_step", "ms_batch", "aux"} and recs[0]["aux"] == 5 * 1.5 and recs[0]["loss"] == 15.0
+    # ... and come back through the load member with the saved content; (b) on_resume receives the resumed step
+    tr2 = _Recorder()
+    b = _Stub(tmp_path / "a", tr2)
+    recs = []
+    fit.fit(_options(niter=12, save=7), tr2, b, b.out, batch_fn=b.batch, log=recs.append, resume=os.path.join(a.out, "training_state", "7.state"))
+    assert [c for c in tr2.calls if c[0] != "step"] == [("on_resume", 7), ("load_extra_state", {"value": 7 * 1.5})]
+    assert tr2.calls.count(("step", None)) == 5 and recs[-1]["iter"] == 12           # the default step_fn is the trainer's step_tensor
+    # (c) another objective: refused, in the words of PERCEPTUAL_RESUME_REFUSAL
+    for other, shown in (("Stub x 3", "Stub x 3"), (None, "none")):
+        tr3 = _Recorder(tag=other)
+        with pytest.raises(ValueError) as e:
+            fit.fit(_options(niter=12, save=7), tr3, _Stub(tmp_path / "a", tr3), a.out, log=recs.append, resume=os.path.join(a.out, "training_state", "7.state"))
+        assert str(e.value) == fit.PERCEPTUAL_RESUME_REFUSAL % ("Stub x 2", shown) and tr3.calls == []
+    # (d) nothing overridden: the file set and the record keys of test_loop_mechanics_checkpoint_cadence_and_exact_resume
+    d = _Stub(tmp_path / "d")
+    recs = d.run(30)
+    assert set(recs[0]) == {"epoch", "iter", "lr", "loss", "ms_per_step", "ms_batch"}
+    for sub, ext in (("models", "_G.pth"), ("training_state", ".state")):
+        assert sorted(os.listdir(os.path.join(d.out, sub))) == sorted("%d%s" % (i, ext) for i in (10, 20, 30))
+    st = torch.load(os.path.join(d.out, "training_state", "30.state"), map_location="cpu", weights_only=False)
+    assert set(st) == {"epoch", "iter", "schedulers", "optimizers", "scaler", fit.STATE_KEY}
+    assert set(st[fit.STATE_KEY]) == {"rng", "epoch_order", "batches_done"}
+
+
+def test_graphed_step_covers_the_trainers_branches_and_invalidates_after_every_replay(monkeypatch):
+    """GraphedStep's bookkeeping without a device (the warm-up and the capture themselves replaced): capture_all covers exactly
+    graph_branches(), step_tensor replays the branch draw_branch() returned, invalidate() follows every replay."""
+    tr = _Recorder(branches=("a", "b", "c"))
+
+    class _Graph:
+        def __init__(self, branch):
+            self.branch = branch
+
+        def replay(self):
+            tr.calls.append(("replay", self.branch))
+
+    def capture(self, branch):
+        tr.calls.append(("capture", branch))
+        self.graphs[branch] = (_Graph(branch), torch.tensor(float(ord(branch))))
+
+    monkeypatch.setattr(train.GraphedStep, "_warm_up", lambda self, branches: tr.calls.append(("warm_up", tuple(branches))))
+    monkeypatch.setattr(train.GraphedStep, "_capture", capture)
+    gt, lq = torch.arange(6.0).reshape(1, 1, 2, 3), -torch.arange(6.0).reshape(1, 1, 2, 3)
+    gs = train.GraphedStep(tr, torch.zeros_like(gt), torch.zeros_like(lq))
+    assert tr.calls == [("warm_up", ("a", "b", "c")), ("invalidate",), ("capture", "a"), ("capture", "b"), ("capture", "c")]
+    assert set(gs.graphs) == {"a", "b", "c"}
+    for branch in ("c", "a", "c", "b"):
+        del tr.calls[:]
+        tr.next_branch = branch
+        loss = gs.step_tensor(gt, lq)
+        assert tr.calls == [("draw_branch",), ("replay", branch), ("invalidate",)] and float(loss) == ord(branch)
+        assert torch.equal(gs.gt, gt) and torch.equal(gs.lr, lq)
+    del tr.calls[:]
+    gs.capture_all()                                   # again (after a resume): the old graphs are dropped, the same set is captured
+    assert [c for c in tr.calls if c[0] == "capture"] == [("capture", b) for b in ("a", "b", "c")] and set(gs.graphs) == {"a", "b", "c"}
+
+
 def test_state_file_interchanges_with_checkpoint_and_stock_torch(tmp_path):
     """5. the driver's `.state` loads with checkpoint.resume_training; schedulers[0] loads into a stock MultiStepLR; the optimizer
     entry carries the CURRENT lr, as torch's param_groups do."""
@@ -219,7 +359,7 @@ def test_state_file_interchanges_with_checkpoint_and_stock_torch(tmp_path):
     o["train"]["lr_steps_rel"] = [0.5]
     fit.fit(o, a.trainer, a, a.out, step_fn=a.step, batch_fn=a.batch, log=lambda r: None)
     path = os.path.join(a.out, "training_state", "25.state")
-    other = types.SimpleNamespace(opt=_stub_opt(lr=1.0))
+    other = _StubTrainer(_stub_opt(lr=1.0))
     sch = fit.make_schedule(other.opt, o)
     epoch, it = checkpoint.resume_training(path, other, [sch])
     assert (epoch, it) == (8, 25) and sch.last_epoch == 25

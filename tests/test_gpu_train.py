@@ -1021,6 +1021,31 @@ def test_adam_skips_parameters_without_gradient_and_graph_replay_invalidates():
     assert "_hip_cache" in netG.RRDB.encoder.mid.block_1.__dict__       # the frozen nets keep theirs
 
 
+def test_stage3_graph_replay_drops_the_decoders_packed_entries_and_keeps_the_frozen_nets():
+    """Stage3Trainer.invalidate() after a GraphedStep replay: every `_packed` entry cached under the deformable decoder is gone, and an
+    entry of the frozen conditional encoder made before the replay is still the SAME object (not dropped and rebuilt)."""
+    from glare_amd import modules as M
+    from glare_amd.synthetic import seeded_init_
+    from glare_amd.train import GraphedStep, Stage3Trainer
+
+    netG = seeded_init_(M.VQLLFLOWDeformable().train(), 0).to(_dev())
+    net_hq = seeded_init_(M.VQModel().eval(), 1).to(_dev())
+    tr = Stage3Trainer(netG, net_hq, lr_G=1e-4, use_msssim=False)
+    g = torch.Generator().manual_seed(14)
+    gt_img = torch.rand(1, 3, 64, 64, generator=g).to(_dev())
+    lr_img = (torch.randn(1, 3, 64, 64, generator=g) * 0.5 - 1.0).to(_dev())
+    gs = GraphedStep(tr, gt_img, lr_img, warmup=2)      # (two: the PackCache builds its job table on entering the second step)
+    with torch.no_grad():
+        netG.reverse_flow_nhwc(net_hq, lr_img)                         # the inference path packs the decoder's and the encoder's filters
+    cached = lambda net: [m for m in net.modules() if m.__dict__.get("_hip_cache")]
+    assert cached(netG.deformable_decoder) and cached(netG.RRDB)
+    frozen = netG.RRDB.encoder.mid.block_1.__dict__["_hip_cache"]
+    key, entry = next(iter(frozen.items()))
+    gs.step_tensor(gt_img, lr_img)
+    assert not cached(netG.deformable_decoder)
+    assert netG.RRDB.encoder.mid.block_1.__dict__["_hip_cache"] is frozen and frozen[key] is entry
+
+
 def test_actnorm_data_dependent_init_matches_reference_vectors(golden, capsys):
     """Row a12: the first training forward of a FRESH flow (every ActNorm all-zero) initialises the 28 step ActNorms and the 96
     coupling-net ActNorms from the batch (FlowActNorms.py:32-46,82-83; flow.py:48-52).  Fixture: what the REFERENCE's 124 bias /

@@ -7,7 +7,7 @@ import types
 import pytest
 import torch
 
-from glare_amd import checkpoint, fit
+from glare_amd import checkpoint, fit, train
 from glare_amd import modules as M
 from glare_amd.train import STAGE1_NEVER_USED
 
@@ -46,12 +46,22 @@ def test_default_options_of_stage1():
 def _stub_opt(lr=1e-4):
     scales = []
     groups = [types.SimpleNamespace(params=[], lr=lr, weight_decay=0.0), types.SimpleNamespace(params=[], lr=lr, weight_decay=0.0)]
-    return types.SimpleNamespace(groups=groups, betas=(0.5, 0.9), eps=1e-8, t=0, set_lr_scale=scales.append, scales=scales)
+    return types.SimpleNamespace(groups=groups, betas=(0.5, 0.9), eps=1e-8, t=0, set_lr_scale=scales.append, scales=scales,
+                                 scaler_state_dict=lambda: dict(checkpoint.GRAD_SCALER_STATE), load_scaler_state_dict=lambda sd: None)
+
+
+class _StubTrainer(train.Trainer):
+    """Stage 1 as the driver sees it, built without a device: an optimizer, the network, and the tag of its checkpoint files."""
+
+    checkpoint_tag = "VQ"
+
+    def __init__(self, net):
+        self.opt, self.netG = _stub_opt(), net
 
 
 class _Stub:
     def __init__(self, out, net):
-        self.trainer = types.SimpleNamespace(opt=_stub_opt(), netG=net, checkpoint_tag="VQ")
+        self.trainer = _StubTrainer(net)
         self.out, self.steps = str(out), []
 
     def __len__(self):
