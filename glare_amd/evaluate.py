@@ -23,7 +23,17 @@ PSNR of two uint8 images is skimage's peak_signal_noise_ratio (Measure.psnr): 10
 NOT built: the `SSIM` / `Adjust_SSIM` / `1_SSIM` columns of Measure.ssim (code/Measure.py:32-41).  It calls
 skimage.structural_similarity(..., multichannel=True) on 2-D arrays, an argument current scikit-image no longer has, and
 scikit-image is not available to pin what it computed; stage 3's `SSIM` column is calculate_ssim (test_stage3.py:202), which is.
-Rows are written in dataset order (the reference prepends each new row).  Without checkpoints the weights are name-seeded."""
+Rows are written in dataset order (the reference prepends each new row).  Without checkpoints the weights are name-seeded.
+
+    python -m glare_amd.evaluate stage1 --run RUN --root LOLdataset [...]          (no --net-vq: the run's own files are the VQGAN)
+
+scores every `RUN/models/*_VQ.pth` of `glare_amd.fit stage1`, the file `--net-vq` takes everywhere else, by the prior's own
+reconstruction of the ground truth (stage1_reconstruct, the protocol of fit.make_validate_stage1): pad bottom / right by symmetric
+reflection to multiples of 4, / 255, encode_nhwc, decode_nhwc(straight_through=True), uint8 of the image's own window.  Columns:
+`PSNR` (psnr_u8), `SSIM` (calculate_ssim on that uint8 image), `codes` = the distinct codes the image's latent uses, `LPIPS` on request.
+Per checkpoint the use of the codebook over every token of the split -- {tokens, active, active_fraction, perplexity} (quantize.py:83-85),
+counted on the device (csrc/vq_usage.hip, metrics.CodebookUsage) -- goes into the record, the closing JSON and the results-stage1.txt
+line, and `<out>/<name>.codes.npy` holds the int64 [K] counts (what basicsr/active_codebook.py plots)."""
 import argparse
 import csv
 import glob
@@ -38,9 +48,12 @@ from . import harness
 from .enhance import check_size, natural_key, write_image
 
 # per-image metric columns in the reference's names and order (test_stage2.py:175-180, test_stage3.py:197-205), without Measure.ssim's
-COLUMNS = {"stage2": ("Adjust_PSNR", "Adjust_LPIPS", "PSNR", "LPIPS"), "stage3": ("PSNR", "SSIM", "1_PSNR", "LPIPS")}
-LEAD = {"stage2": ("conf", "heat", "name"), "stage3": ("conf", "name")}
+COLUMNS = {"stage1": ("PSNR", "SSIM", "codes", "LPIPS"), "stage2": ("Adjust_PSNR", "Adjust_LPIPS", "PSNR", "LPIPS"),
+           "stage3": ("PSNR", "SSIM", "1_PSNR", "LPIPS")}
+LEAD = {"stage1": ("conf", "name"), "stage2": ("conf", "heat", "name"), "stage3": ("conf", "name")}
+CHECKPOINT_TAG = {"stage1": "VQ", "stage2": "G", "stage3": "G"}       # <iter>_<tag>.pth: what glare_amd.fit writes for the stage
 LOWER_IS_BETTER = ("LPIPS", "Adjust_LPIPS")
+NET_VQ_REFUSAL = "--net-vq is not a stage1 option: the run's own <iter>_VQ.pth files are the VQGAN that is scored"
 WARM_SIDE = 32          # the side of the one-image pass that rebuilds every packed filter after a checkpoint swap
 
 
@@ -57,6 +70,58 @@ def stage2_pads(h, w):
         raise ValueError("stage 2: the image size %dx%d pads to %dx%d, not a multiple of 4 on both sides: the VQGAN decoder would "
                          "return %dx%d" % (h, w, hp, wp, hp // 4 * 4, wp // 4 * 4))
     return pads
+
+
+def stage1_pads(h, w):
+    """(top, bottom, left, right): bottom / right up to multiples of 4, the encoder's stride."""
+    return (0, -h % 4, 0, -w % 4)
+
+
+def stage1_reconstruct(net, highs, precision=None):
+    """The stage-1 protocol on uint8 ground-truth images `highs` [n,h,w,3] (host): padded bottom / right by symmetric reflection to
+    multiples of 4, / 255, VQModel.encode_nhwc, decode_nhwc(want_image=True, straight_through=True) as stages 2 and 3 call them ->
+    (img fp32 NCHW [n,3,hp,wp], gt uint8 [n,h,w,3], u8 = rgb(img) of the image's own window, sse int64 [n], idx int64 [n * hp/4 * wp/4]),
+    all on the device and nothing read back.  PSNR: harness.psnr_u8(sse, 3 h w).  The caller sets eval mode and no_grad."""
+    import torch
+
+    from . import ops
+
+    highs = np.asarray(highs)
+    assert highs.dtype == np.uint8 and highs.ndim == 4 and highs.shape[3] == 3, (highs.dtype, highs.shape)
+    n, h, w, _ = highs.shape
+    _, pb, _, pr = stage1_pads(h, w)
+    padded = np.pad(highs, [(0, 0), (0, pb), (0, pr), (0, 0)], "symmetric")
+    with ops.use_precision(ops.inference_precision(precision)):
+        x = torch.from_numpy(np.ascontiguousarray(padded.transpose(0, 3, 1, 2)).astype(np.float32) / 255).cuda()
+        idx, img, _ = net.decode_nhwc(net.encode_nhwc(x), want_image=True, straight_through=True)
+        img = img.float().contiguous()
+        gt = torch.from_numpy(np.array(highs)).cuda()                            # (a copy: the dataset's arrays are read-only)
+        u8, sse = harness.score_device(img, gt, window=(0, 0, h, w))
+    return img, gt, u8, sse, idx
+
+
+def _device_rows_stage1(net, highs, precision, lpips_net, want_images, usage):
+    """One stage-1 batch -> ({column: host float64 [n]}, non-finite counts [n], {image kind: uint8 device tensor}, counts int64 [n, K] on
+    the device: what this batch added to `usage`)."""
+    import torch
+
+    from . import ops
+
+    n, h, w, _ = highs.shape
+    with torch.no_grad():
+        img, gt, u8, sse, idx = stage1_reconstruct(net, highs, precision)
+        _, bad = harness.postprocess_unpaired_device(img, (0, 0, 0, 0), h, w, want_nonfinite=True)            # the overflow flag only
+        counts, _ = usage.update(idx, groups=n)
+        cols = {"PSNR": sse, "SSIM": harness.ssim_device(u8.float() / 255, gt), "codes": ops.vq_usage_stats(counts)[1].double()}
+        if lpips_net is not None:
+            from . import metrics
+
+            cols["LPIPS"] = lpips_net(metrics.to_lpips_input(u8), metrics.to_lpips_input(gt)).view(-1).double()
+    host = {}
+    for c, v in cols.items():
+        v = v.cpu().numpy()
+        host[c] = np.array([harness.psnr_u8(s, 3 * h * w) for s in v]) if v.dtype == np.int64 else v.astype(np.float64)
+    return host, bad.cpu().numpy(), ({"": u8} if want_images else {}), counts
 
 
 def _device_rows(stage, netG, net_hq, low_d, gt_d, precision, lpips_net, want_images):
@@ -114,7 +179,10 @@ def score_checkpoint(stage, netG, net_hq, lows, gts, batch=8, precision=None, lp
     assert lows.dtype == np.uint8 and gts.dtype == np.uint8 and lows.ndim == 4 and lows.shape == gts.shape and lows.shape[3] == 3
     n, h, w, _ = lows.shape
     batch = max(1, min(batch, n))
-    if stage == "stage2":
+    if stage == "stage1":
+        pads = stage1_pads(h, w)
+        check_size(h + pads[1], w + pads[3], batch)
+    elif stage == "stage2":
         pads = stage2_pads(h, w)
         check_size(h + pads[1], w + pads[3], batch)
     else:
@@ -122,21 +190,32 @@ def score_checkpoint(stage, netG, net_hq, lows, gts, batch=8, precision=None, lp
     assert torch.cuda.is_available(), "glare_amd.evaluate needs an MI355X: the HIP kernels are the only implementation"
     device = device or torch.device("cuda", torch.cuda.current_device())
     precision = ops.inference_precision(precision)
-    lows_p, gts_p = torch.from_numpy(lows).pin_memory(), torch.from_numpy(gts).pin_memory()
+    usage = None
+    if stage == "stage1":           # the prior reconstructs the ground truth: `lows` is not read
+        from . import metrics
 
-    def run(lo, hi, prec):
-        return _device_rows(stage, netG, net_hq, lows_p[lo:hi].to(device, non_blocking=True), gts_p[lo:hi].to(device, non_blocking=True),
-                            prec, lpips_net, keep_images)
+        usage = metrics.CodebookUsage(netG.quantize.n_e, device)
+
+        def run(lo, hi, prec):
+            return _device_rows_stage1(netG, gts[lo:hi], prec, lpips_net, keep_images, usage)
+    else:
+        lows_p, gts_p = torch.from_numpy(lows).pin_memory(), torch.from_numpy(gts).pin_memory()
+
+        def run(lo, hi, prec):
+            return _device_rows(stage, netG, net_hq, lows_p[lo:hi].to(device, non_blocking=True), gts_p[lo:hi].to(device, non_blocking=True),
+                                prec, lpips_net, keep_images) + (None,)
 
     rows, reruns, kept = [None] * n, [], {}
     for lo in range(0, n, batch):
         hi = min(lo + batch, n)
-        cols, bad, images = run(lo, hi, precision)
+        cols, bad, images, counts = run(lo, hi, precision)
         images = {k: v.cpu().numpy() for k, v in images.items()}
         for j in range(hi - lo):
             flagged = int(bad[j]) > 0 or not all(math.isfinite(cols[c][j]) or cols[c][j] == math.inf for c in cols)
             if flagged and precision != "bf16":       # fp16 overflow: bf16 has fp32's range, same kernels; a flagged exception
-                c1, _, im1 = run(lo + j, lo + j + 1, "bf16")
+                if usage is not None:
+                    usage.discard(counts[j])          # the re-run's indices are the ones that count
+                c1, _, im1, _ = run(lo + j, lo + j + 1, "bf16")
                 for c in cols:
                     cols[c][j] = c1[c][0]
                 for k in images:
@@ -146,6 +225,9 @@ def score_checkpoint(stage, netG, net_hq, lows, gts, batch=8, precision=None, lp
         for k, v in images.items():
             kept.setdefault(k, []).append(v)
     if report is not None:
+        if usage is not None:
+            report["codebook"] = usage.stats()
+            report["codes"] = usage.counts().cpu().numpy()
         report["bf16_rerun_images"] = reruns
         if keep_images:
             report["images"] = {k: np.concatenate(v) for k, v in kept.items()}
@@ -153,11 +235,11 @@ def score_checkpoint(stage, netG, net_hq, lows, gts, batch=8, precision=None, lp
 
 
 # ---- the sweep ----------------------------------------------------------------------------------------------------------------
-def list_checkpoints(run_or_files):
-    """A run folder -> its models/*_G.pth in natural order (natsorted(os.listdir(.../models)), test_stage2.py:110); a list of
-    files -> the same order."""
+def list_checkpoints(run_or_files, stage="stage2"):
+    """A run folder -> its models/*_G.pth (stage1: *_VQ.pth) in natural order (natsorted(os.listdir(.../models)), test_stage2.py:110);
+    a list of files -> the same order."""
     if isinstance(run_or_files, (str, os.PathLike)):
-        files = glob.glob(os.path.join(run_or_files, "models", "*_G.pth"))
+        files = glob.glob(os.path.join(run_or_files, "models", "*_%s.pth" % CHECKPOINT_TAG[stage]))
     else:
         files = list(run_or_files)
     return sorted(files, key=natural_key)
@@ -185,7 +267,12 @@ def warm(stage, netG, net_hq, precision=None, device=None):
 
     lr = torch.zeros(1, 3, WARM_SIDE, WARM_SIDE, dtype=torch.float32, device=device)
     with torch.no_grad():
-        if stage == "stage2":
+        if stage == "stage1":
+            from . import ops
+
+            with ops.use_precision(ops.inference_precision(precision)):
+                netG.decode_nhwc(netG.encode_nhwc(lr), want_image=True, straight_through=True)
+        elif stage == "stage2":
             netG.enhance_nhwc(net_hq, lr, precision=precision)
         else:
             netG.reverse_flow_nhwc(net_hq, lr, precision=precision)
@@ -195,7 +282,19 @@ def build_nets(stage, net_vq=None, device=None):
     """(netG, net_hq) of the stage as glare_amd.fit builds them, in eval mode: name-seeded, the VQGAN from `net_vq` if given."""
     from . import checkpoint
 
+    if stage == "stage1" and net_vq:
+        raise ValueError(NET_VQ_REFUSAL)
     return checkpoint.build_nets(stage, net_vq=net_vq, device=device)
+
+
+USAGE_KEYS = ("tokens", "active", "active_fraction", "perplexity")     # the `codebook` block of a stage-1 record
+
+
+def _usage_block(codes):
+    """The `codebook` block from a host histogram (a resumed sweep's `<name>.codes.npy`), in float64."""
+    from . import metrics
+
+    return metrics.usage_block_host(codes)
 
 
 def _read_csv_means(path, cols):
@@ -213,7 +312,7 @@ def sweep(stage, run_or_files, out_dir, lows, gts, names=None, nets=None, select
     cols = columns(stage, lpips_net is not None)
     if select not in cols:
         raise ValueError("--select %s: %s produces the columns %s" % (select, stage, ", ".join(cols)))
-    files = list_checkpoints(run_or_files)
+    files = list_checkpoints(run_or_files, stage)
     n = len(lows)
     names = list(names) if names is not None else ["%d.png" % i for i in range(n)]
     conf = conf or "train_%s_LOL" % stage
@@ -234,8 +333,11 @@ def sweep(stage, run_or_files, out_dir, lows, gts, names=None, nets=None, select
     for path in files:
         name = os.path.splitext(os.path.basename(path))[0]
         csv_path = os.path.join(out_dir, name + ".csv")
+        codes_path = os.path.join(out_dir, name + ".codes.npy")       # stage 1: the int64 [K] use of the codebook over the split
         if os.path.isfile(csv_path):                                  # resumed sweep (test_stage2.py:126-127)
             done.append({"name": name, "means": _read_csv_means(csv_path, cols), "skipped": True})
+            if stage == "stage1" and os.path.isfile(codes_path):
+                done[-1]["codebook"] = _usage_block(np.load(codes_path))
             continue
         t0 = time.perf_counter()
         load_fn(path, netG)
@@ -253,15 +355,23 @@ def sweep(stage, run_or_files, out_dir, lows, gts, names=None, nets=None, select
             wr.writeheader()
             for nm, row in zip(names, rows):
                 wr.writerow({**{k: (nm if k == "name" else lead[k]) for k in LEAD[stage]}, **{c: repr(row[c]) for c in cols}})
-        os.replace(csv_path + "_", csv_path)
         means = {c: float(np.mean([r[c] for r in rows])) for c in cols}
+        codebook = None
+        if report.get("codes") is not None:                          # written before the CSV: a CSV that exists has its counts beside it
+            codes = np.asarray(report["codes"], dtype=np.int64)
+            np.save(codes_path, codes)
+            codebook = {k: v for k, v in (report.get("codebook") or _usage_block(codes)).items() if k in USAGE_KEYS}
+        os.replace(csv_path + "_", csv_path)
         with open(results_path, "a") as f:
-            f.write("%s %s\n" % (name, format_measurements(means)))
+            usage_text = ", " + format_measurements({"codebook_" + k: v for k, v in codebook.items()}) if codebook else ""
+            f.write("%s %s%s\n" % (name, format_measurements(means), usage_text))
         for kind, imgs in report.get("images", {}).items():
             for nm, im in zip(names, imgs):
                 write_image(os.path.join(out_dir, name, kind, nm), im)
         rec = {"name": name, "means": means, "skipped": False, "seconds_load_repack": round(t1 - t0, 4), "seconds_scoring": round(t2 - t1, 4),
                "bf16_rerun_images": [names[i] for i in report.get("bf16_rerun_images", [])]}
+        if codebook:
+            rec["codebook"] = codebook
         done.append(rec)
         if log:
             log(rec)
@@ -274,7 +384,8 @@ def sweep(stage, run_or_files, out_dir, lows, gts, names=None, nets=None, select
         best = {"name": b["name"], "column": select, "value": b["means"][select]}
     mean = lambda key: round(float(np.mean([d[key] for d in scored])), 4) if scored else None
     secs = sum(d["seconds_scoring"] for d in scored)
-    return {"stage": stage, "images": n, "checkpoints": done, "best": best, "select": select,
+    usage = {"codebook": {d["name"]: d["codebook"] for d in done if "codebook" in d}} if stage == "stage1" else {}
+    return {"stage": stage, "images": n, "checkpoints": done, "best": best, "select": select, **usage,
             "seconds_per_checkpoint": {"load_repack": mean("seconds_load_repack"), "scoring": mean("seconds_scoring")},
             "images_per_sec_scoring": round(n * len(scored) / secs, 2) if secs > 0 else None,
             "bf16_rerun_images": {d["name"]: d["bf16_rerun_images"] for d in scored if d["bf16_rerun_images"]},
@@ -287,7 +398,7 @@ def main(argv=None):
 
     ap = argparse.ArgumentParser(description="Score every checkpoint of a training run on the test split.")
     ap.add_argument("stage", choices=sorted(COLUMNS))
-    ap.add_argument("--run", required=True, help="run folder of glare_amd.fit: <run>/models/<iter>_G.pth")
+    ap.add_argument("--run", required=True, help="run folder of glare_amd.fit: <run>/models/<iter>_G.pth (stage1: <iter>_VQ.pth)")
     ap.add_argument("--root", required=True, help="dataset folder (v1: <root>/eval15/{low,high}; v2: see --layout)")
     ap.add_argument("--layout", choices=sorted(D.LAYOUTS), default="v1")
     ap.add_argument("--net-vq", default=None, help="VQGAN checkpoint (reference format); without it the weights are name-seeded")
@@ -300,6 +411,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--save-images", action="store_true", help="write the scored uint8 images under <out>/<name>/")
     args = ap.parse_args(argv)
+    if args.stage == "stage1" and args.net_vq:
+        ap.error(NET_VQ_REFUSAL)
     import torch
 
     if args.select not in columns(args.stage, args.lpips):

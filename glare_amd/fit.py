@@ -7,6 +7,7 @@ code/train_stage3.py:138-300 over models/base_model.py:46-83 and models/lr_sched
     python -m glare_amd.fit stage3 --root LOLdataset --out run --resume run/training_state/500.state
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --vgg16 vgg16.pth --lpips-heads vgg.pth [--gan]
     python -m glare_amd.fit stage3 --root LOLdataset --out run --net-g stage2_G.pth --net-vq vqgan.pkl --vgg16 vgg16.pth
+    python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-usage        (log the codebook's use; glare_amd.evaluate stage1 scores the run)
 
 Stage 1 trains the VQGAN prior itself (VQModel_arch.py:98-101, 148-157) on the ground-truth half of the pairs and writes
 <out>/models/<iter>_VQ.pth under the reference's VQModel key names: what `--net-vq` of stages 2 and 3, `evaluate` and `enhance` load.
@@ -316,11 +317,12 @@ def build_perceptual(stage, device, vgg16=None, lpips_heads=None):
 
 
 def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16", gan=False, net_d=None, vgg16=None,
-                  lpips_heads=None, perceptual_weight=None):
+                  lpips_heads=None, perceptual_weight=None, codebook_usage=False):
     """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer.  gan (stage 1 only): with the
     patch discriminator (taming's initialisation under the run's seed, or the `_D.pth` file net_d).  vgg16 / lpips_heads: the weight
     files of the perceptual term (stage 1: LPIPS, both files; stage 3: the VGG16-feature loss, the backbone alone); perceptual_weight:
-    stage 1's factor on it (default 1.0).  The loss network is frozen and is written to no checkpoint: a resumed run names the files again."""
+    stage 1's factor on it (default 1.0).  The loss network is frozen and is written to no checkpoint: a resumed run names the files again.
+    codebook_usage (stage 1 only): Stage1Trainer's; off, the trainer is built without the keyword."""
     from . import modules as M
 
     check_perceptual_options(stage, vgg16, lpips_heads, perceptual_weight)
@@ -330,6 +332,8 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
         raise ValueError(GRAPH_REFUSAL)
     if stage != "stage1" and gan:
         raise ValueError(GAN_REFUSAL)
+    if stage != "stage1" and codebook_usage:
+        raise ValueError(CODEBOOK_USAGE_REFUSAL)
     netG, net_hq = checkpoint.build_nets(stage, True, net_g, net_vq, options, device)
     if stage == "stage1":
         disc = None
@@ -343,7 +347,8 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
                                    codebook_weight=tr.get("codebook_weight", 1.0), precision=precision, discriminator=disc,
                                    disc_start=tr.get("disc_start", 10000), disc_weight=tr.get("disc_weight", 0.8),
                                    disc_factor=tr.get("disc_factor", 1.0), perceptual=perceptual,
-                                   perceptual_weight=1.0 if perceptual_weight is None else float(perceptual_weight))
+                                   perceptual_weight=1.0 if perceptual_weight is None else float(perceptual_weight),
+                                   **({"codebook_usage": True} if codebook_usage else {}))
     if stage == "stage2":
         return train.Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
                                    train_rrdb=bool(options["network_G"].get("train_RRDB", False)), precision=precision)
@@ -351,6 +356,8 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
                                perceptual=perceptual)
 
 
+CODEBOOK_USAGE_REFUSAL = ("--codebook-usage is a stage1 option: stage1 is the stage that trains the codebook (stages 2 and 3 read a frozen one; "
+                          "glare_amd.evaluate stage1 reports the use of a finished prior's)")
 GAN_REFUSAL = "--gan is a stage1 option: the patch discriminator belongs to the VQGAN prior's objective (stages 2 and 3 train no GAN term)"
 LPIPS_REFUSAL = ("stage1's perceptual term is LPIPS and needs both files: --vgg16 (the VGG16 backbone) and --lpips-heads (the five linear "
                  "heads, taming's / the lpips package's vgg.pth); one without the other would leave half the network at its initialisation")
@@ -407,27 +414,31 @@ def make_validate(trainer, test_ds, precision, batch=8):
 def make_validate_stage1(trainer, test_ds, precision):
     """Mean PSNR of decode(encode(gt)) over the test split's ground-truth images, through the inference kernels (VQModel.encode_nhwc /
     decode_nhwc as stages 2 and 3 call them); an image whose sides are no multiple of 4 (the encoder's stride) is padded at the
-    bottom / right by reflection and scored on its own window.  uint8 PSNR as glare_amd.evaluate (harness.score_device / psnr_u8)."""
-    from . import harness, ops
+    bottom / right by reflection and scored on its own window.  uint8 PSNR as glare_amd.evaluate (harness.score_device / psnr_u8): the
+    protocol is evaluate.stage1_reconstruct, one image at a time.  A trainer built with codebook_usage=True also gets `codebook`, the use of
+    the codebook over every token of the split ({tokens, active, active_fraction, perplexity}, metrics.CodebookUsage)."""
+    from . import evaluate, harness, metrics
 
     def validate(step):
         net = trainer.netG
         was_training = net.training
         net.eval()
         vals = []
+        usage = metrics.CodebookUsage(net.quantize.n_e, next(net.parameters()).device) if getattr(trainer, "codebook_usage", False) else None
         try:
-            with torch.no_grad(), ops.use_precision(ops.inference_precision(precision)):
+            with torch.no_grad():
                 for _, high, _ in test_ds.pairs:
                     h, w = high.shape[:2]
-                    padded = np.pad(high, [(0, -h % 4), (0, -w % 4), (0, 0)], "symmetric")
-                    x = torch.from_numpy(np.ascontiguousarray(padded.transpose(2, 0, 1)[None]).astype(np.float32) / 255).cuda()
-                    _, img, _ = net.decode_nhwc(net.encode_nhwc(x), want_image=True, straight_through=True)
-                    gt = torch.from_numpy(np.array(high[None])).cuda()                   # (a copy: the dataset's arrays are read-only)
-                    _, sse = harness.score_device(img.float().contiguous(), gt, window=(0, 0, h, w))
+                    _, _, _, sse, idx = evaluate.stage1_reconstruct(net, high[None], precision)
+                    if usage is not None:
+                        usage.update(idx)
                     vals.append(harness.psnr_u8(int(sse[0]), 3 * h * w))
         finally:
             net.train(was_training)
-        return {"images": len(vals), "psnr": float(np.mean(vals))}
+        res = {"images": len(vals), "psnr": float(np.mean(vals))}
+        if usage is not None:
+            res["codebook"] = {k: v for k, v in usage.stats().items() if k in evaluate.USAGE_KEYS}
+        return res
 
     return validate
 
@@ -459,8 +470,12 @@ def parse_args(argv=None):
                                                   "stage1 with --lpips-heads: the LPIPS term; stage3: the VGG16-feature perceptual term")
     ap.add_argument("--lpips-heads", default=None, help="stage1: the LPIPS linear heads (taming's / the lpips package's vgg.pth)")
     ap.add_argument("--perceptual-weight", type=float, default=None, help="stage1: factor on the LPIPS term (default 1.0)")
+    ap.add_argument("--codebook-usage", action="store_true", help="stage1: log codebook_active / codebook_perplexity of every step's indices, and "
+                                                                   "the test split's codebook use with the closing validation")
     ap.add_argument("--no-val", action="store_true", help="skip the closing validation")
     args = ap.parse_args(argv)
+    if args.codebook_usage and args.stage != "stage1":
+        ap.error(CODEBOOK_USAGE_REFUSAL)
     if args.graph and args.stage == "stage1":
         ap.error(GRAPH_REFUSAL)
     if args.gan and args.stage != "stage1":
@@ -505,7 +520,8 @@ def main(argv=None):
     host_ds = D.LAYOUTS[args.layout](train_opt, train=True, all_opt=options)
     dataset = D.DeviceLoLDataset(host_ds, device)
     trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision, gan=args.gan, net_d=net_d,
-                            vgg16=args.vgg16, lpips_heads=args.lpips_heads, perceptual_weight=args.perceptual_weight)
+                            vgg16=args.vgg16, lpips_heads=args.lpips_heads, perceptual_weight=args.perceptual_weight,
+                            codebook_usage=args.codebook_usage)
     if args.vgg16:        # the opening line of a run with a perceptual term: which files it was built from
         print(json.dumps({"perceptual": type(trainer.perceptual).__name__, "vgg16": args.vgg16, "lpips_heads": args.lpips_heads,
                           "tensors_loaded": len(trainer.perceptual.loaded_keys)}), flush=True)

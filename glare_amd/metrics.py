@@ -167,6 +167,59 @@ def to_lpips_input(imgs_u8):
     return imgs_u8.permute(0, 3, 1, 2).float() / 127.5 - 1
 
 
+class CodebookUsage:
+    """Running use of the codebook over a split (basicsr/active_codebook.py's count; the perplexity of quantize.py:83-85 over every token
+    seen): `update(idx, groups)` adds one batch's indices to an int64 [n_codes] total on the device -- kernel launches only, no host
+    synchronisation -- and returns that batch's per-group counts; `stats()` reads the totals back."""
+
+    def __init__(self, n_codes, device):
+        self.n_codes = int(n_codes)
+        self._total = torch.zeros(self.n_codes, dtype=torch.int64, device=device)
+        self._oor = torch.zeros((), dtype=torch.int64, device=device)
+
+    def update(self, idx, groups=1):
+        """-> (counts int64 [groups, n_codes], out_of_range int64 [groups]) of this batch (device tensors)."""
+        from . import ops
+
+        counts, oor, _ = ops.vq_usage(idx, self.n_codes, groups, total=self._total)
+        self._oor += oor.sum()
+        return counts, oor
+
+    def discard(self, counts_row):
+        """Takes one group's counts (a row update() returned) out of the total again: an image that is scored a second time."""
+        self._total -= counts_row
+
+    def counts(self):
+        """The int64 [n_codes] total (the device tensor itself)."""
+        return self._total
+
+    def reset(self):
+        self._total.zero_()
+        self._oor.zero_()
+
+    def stats(self):
+        from . import ops
+
+        tokens, active, _, perplexity = ops.vq_usage_stats(self._total)
+        return usage_block(int(tokens), int(active), float(perplexity), self.n_codes, int(self._oor))
+
+
+def usage_block(tokens, active, perplexity, n_codes, out_of_range=None):
+    """The `codebook` block of a record: host numbers."""
+    block = {"tokens": int(tokens), "active": int(active), "active_fraction": int(active) / int(n_codes), "perplexity": float(perplexity)}
+    if out_of_range is not None:
+        block["out_of_range"] = int(out_of_range)
+    return block
+
+
+def usage_block_host(counts):
+    """usage_block of a host int64 [K] histogram, in float64 (a resumed sweep reads `<name>.codes.npy` back; no device involved)."""
+    counts = np.asarray(counts, dtype=np.int64)
+    n = int(counts.sum())
+    p = counts[counts > 0].astype(np.float64) / max(n, 1)
+    return usage_block(n, int((counts > 0).sum()), float(np.exp(-np.sum(p * np.log(p + 1e-10)))), counts.size)
+
+
 class Measure:
     """Measure (Measure.py:17-30), the LPIPS leg: `lpips(imgA, imgB)` on uint8 HWC images (numpy or device tensors) -> float."""
 

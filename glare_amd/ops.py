@@ -26,6 +26,42 @@ def vq_nearest(z_tokens, codebook, want_zq=True):
     return idx, zq
 
 
+def vq_usage(idx, n_codes, groups=1, total=None):
+    """idx: int64 indices, `groups` equal runs of tokens (one run = one image's latent) -> (counts int64 [groups, n_codes], out_of_range
+    int64 [groups], total).  total: int64 [n_codes] the counts of every group are ADDED to (None: a new one, zeros before the call).
+    An index outside [0, n_codes) selects nothing and is counted in out_of_range.  Exact, no atomics in global memory (csrc/vq_usage.hip)."""
+    require_cuda(idx, total)
+    assert idx.dtype == torch.int64 and groups >= 1 and idx.numel() > 0 and idx.numel() % groups == 0, (idx.dtype, idx.numel(), groups)
+    idx = idx.contiguous()
+    n = idx.numel() // groups
+    if total is None:
+        total = torch.zeros(n_codes, dtype=torch.int64, device=idx.device)
+    assert total.dtype == torch.int64 and tuple(total.shape) == (n_codes,) and total.is_contiguous() and total.device == idx.device
+    lib = _lib.main_lib()
+    nws = lib.glare_vq_usage_workspace_bytes(groups, n, n_codes)
+    ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=idx.device)
+    counts = torch.empty(groups, n_codes, dtype=torch.int64, device=idx.device)
+    oor = torch.empty(groups, dtype=torch.int64, device=idx.device)
+    check(lib.glare_vq_usage_i64(ptr(idx), groups, n, n_codes, ptr(counts), ptr(oor), ptr(total), ptr(ws), nws, stream_handle()),
+          "glare_vq_usage_i64")
+    return counts, oor, total
+
+
+def vq_usage_stats(counts):
+    """counts: int64 [R, K] (or [K]: one row) of non-negative counts -> (tokens int64, active int64, entropy fp64, perplexity fp64), each
+    [R] (or 0-d): quantize.py:84-85 in fp64 from the exact counts; a row without tokens has perplexity 1."""
+    require_cuda(counts)
+    assert counts.dtype == torch.int64 and counts.dim() in (1, 2) and counts.numel() > 0, (counts.dtype, tuple(counts.shape))
+    rows = counts.contiguous().view(-1, counts.shape[-1])
+    R, K = rows.shape
+    tokens, active = (torch.empty(R, dtype=torch.int64, device=rows.device) for _ in range(2))
+    entropy, perplexity = (torch.empty(R, dtype=torch.float64, device=rows.device) for _ in range(2))
+    check(_lib.main_lib().glare_vq_usage_stats(ptr(rows), R, K, ptr(tokens), ptr(active), ptr(entropy), ptr(perplexity), stream_handle()),
+          "glare_vq_usage_stats")
+    out = (tokens, active, entropy, perplexity)
+    return tuple(t[0] for t in out) if counts.dim() == 1 else out
+
+
 # ---- convolution --------------------------------------------------------------------------------
 # Every constant and both structs of this section are read from include/glare_hip.h (_lib.constants(), _lib.structs()).
 _K = _lib.constants()

@@ -275,6 +275,7 @@ STAGE1_NEVER_USED = ("conv_semantic.",)
 
 DISC_KEY = "discriminator"   # stage 1 with a discriminator: its Adam and GradScaler state dicts, one more top-level key of a `.state` file
 GAN_TERMS = ("g_loss", "d_weight", "d_loss")
+USAGE_TERMS = ("codebook_active", "codebook_perplexity")      # Stage1Trainer(codebook_usage=True)
 
 
 def two_group_adam(params, lr, weight_decay, never_used=(), second=(), second_lr=None, second_weight_decay=0.0, betas=(0.9, 0.999),
@@ -494,10 +495,16 @@ class Stage1Trainer(Trainer):
     checkpoint_tag = "VQ"                            # glare_amd.fit: <out>/models/<iter>_VQ.pth, the file `--net-vq` takes
 
     def __init__(self, net, lr_G=1e-4, weight_decay_G=0.0, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0,
-                 device_state=False, precision="fp16", discriminator=None, disc_start=10000, disc_weight=0.8, disc_factor=1.0):
+                 device_state=False, precision="fp16", discriminator=None, disc_start=10000, disc_weight=0.8, disc_factor=1.0,
+                 codebook_usage=False):
         """lr_G: a starting point, not a tuned value (the reference sets `self.learning_rate` from a config it does not ship).
         discriminator: an NLayerDiscriminator on the net's device, or None (no GAN term: the step and every file are what they were);
-        disc_start / disc_weight / disc_factor: taming's defaults for the VQGAN configs."""
+        disc_start / disc_weight / disc_factor: taming's defaults for the VQGAN configs.
+        codebook_usage: every step also puts `codebook_active` (int64: the distinct codes the step's indices select) and
+        `codebook_perplexity` (fp64, quantize.py:83-85) of that forward pass into last_terms -- three small launches (csrc/vq_usage.hip), no
+        host synchronisation; off (the default), the step launches and records what it always did.  Usage is not state: nothing of it
+        is written to a `.state` file."""
+        self.codebook_usage = bool(codebook_usage)
         self.codebook_weight, self.perceptual, self.perceptual_weight = float(codebook_weight), perceptual, float(perceptual_weight)
         for p in net.parameters():
             p.requires_grad_(True)
@@ -537,7 +544,13 @@ class Stage1Trainer(Trainer):
         self.global_step = step                      # what `disc_start` is compared with
 
     def log_terms(self):
-        return (GAN_TERMS if self.discriminator is not None else ()) + super().log_terms()
+        return (GAN_TERMS if self.discriminator is not None else ()) + super().log_terms() + (USAGE_TERMS if self.codebook_usage else ())
+
+    def _usage_terms(self, idx):
+        """{codebook_active, codebook_perplexity} of one forward pass's indices, device tensors."""
+        counts, _, _ = ops.vq_usage(idx, self.net.quantize.n_e)
+        _, active, _, perplexity = ops.vq_usage_stats(counts)
+        return {"codebook_active": active[0], "codebook_perplexity": perplexity[0]}
 
     def invalidate(self):
         self.net.invalidate()
@@ -557,11 +570,13 @@ class Stage1Trainer(Trainer):
         with ops.use_precision(self.precision):
             self.opt.zero_grad()
             with self.pack_cache:
-                xrec, qloss, _ = self.net.train_nhwc(gt)
+                xrec, qloss, idx = self.net.train_nhwc(gt)
                 loss, self.last_terms = stage1_loss(xrec, gt, qloss, self.codebook_weight, self.perceptual, self.perceptual_weight)
                 self.opt.scale_loss(loss).backward()
             self.opt.step()
         self.net.invalidate()                        # packed inference weights are stale now
+        if self.codebook_usage:
+            self.last_terms.update(self._usage_terms(idx))
         if self.discriminator is not None:           # before disc_start: f = 0, nothing of D launched, its parameters and optimizer untouched
             self.last_terms.update(g_loss=self._zero, d_weight=self._zero, d_loss=self._zero)
         return loss.detach()
@@ -580,7 +595,7 @@ class Stage1Trainer(Trainer):
             self.opt_d.zero_grad()
             self.opt_d.state3[2:3].copy_(self.opt.state3[2:3])       # D's lr follows the generator's schedule (one device scalar)
             with self.pack_cache:
-                xrec, qloss, _ = self.net.train_nhwc(gt)
+                xrec, qloss, idx = self.net.train_nhwc(gt)
                 # the two gradients at xrec, on a detached leaf: nll's and, through D (data gradients only), g_loss's.  Both carry the
                 # generator's loss scale s (fp16: 1 / n of a mean is an fp16 subnormal unscaled), divided out of the norms below
                 xr = xrec.detach().requires_grad_(True)
@@ -611,6 +626,8 @@ class Stage1Trainer(Trainer):
         loss = nll.detach() + d_weight * f * g_loss.detach() + cb.detach()
         terms["codebook_loss"] = cb
         terms.update(g_loss=g_loss.detach(), d_weight=d_weight, d_loss=d_loss.detach())
+        if self.codebook_usage:
+            terms.update(self._usage_terms(idx))
         self.last_terms = terms
         return loss
 

@@ -79,6 +79,32 @@ int glare_vq_backward_f32(const float* z_nhwc, const float* zq_nhwc, const long 
                           const float* gl_dev, long long n_tokens, int n_codes, int dim, float cz, float ce, float* dz_nhwc,
                           float* dE, void* workspace, size_t workspace_bytes, glare_stream_t stream);
 
+/* ---- a5, usage: which codes the indices select (csrc/vq_usage.hip) ---------------------------------------------
+ * VectorQuantizer2 returns perplexity = None (code/models/modules/quantize.py:286); the older VectorQuantizer computes it
+ * (quantize.py:83-85: e_mean = mean(one_hot(idx), 0); perplexity = exp(-sum(e_mean * log(e_mean + 1e-10)))) and the vendored
+ * basicsr/active_codebook.py counts index use over a test set.  Both are statistics of the histogram built here.
+ * glare_vq_usage_i64: idx_i64 [groups][n_tokens] int64 (the indices of glare_vq_nearest_f32; a group = one image's latent) ->
+ *   counts       [groups][n_codes] int64, written: tokens of the group that select each code
+ *   out_of_range [groups] int64, written: indices < 0 or >= n_codes; they select no code and address no memory
+ *   total        [n_codes] int64 or NULL, ADDED TO: total[k] += sum_g counts[g][k], from the same pass (a test split's running sum)
+ * Exact integers: LDS integer adds per token span, partial rows summed in a fixed order; no global or float atomics; the same bits
+ * on every run.  workspace: glare_vq_usage_workspace_bytes(groups, n_tokens, n_codes) bytes (0: not a shape the kernels take).
+ * n_codes <= GLARE_VQ_USAGE_TIER is one pass over the indices, a larger one ceil(n_codes / TIER) passes.
+ * GLARE_ERR_INVALID: a null pointer (total excepted) or a non-positive size; GLARE_ERR_UNSUPPORTED: n_codes > GLARE_VQ_USAGE_MAX_CODES,
+ * groups > 65535, n_tokens > 64 (2^32 - 1); GLARE_ERR_WORKSPACE as elsewhere.
+ * glare_vq_usage_stats: counts [rows][n_codes] int64, every count >= 0 (per-group rows and the total alike) -> per row
+ *   tokens = sum_k c_k (int64), active = #{k: c_k > 0} (int64), entropy = -sum_k p_k log(p_k + 1e-10), perplexity = exp(entropy),
+ *   p_k = c_k / tokens: fp64 from the exact counts, the K terms added in a fixed order.  A row with tokens == 0: active 0, entropy 0,
+ *   perplexity 1 (the sum is empty), never NaN. */
+#define GLARE_VQ_USAGE_TIER 8192        /* codes histogrammed per pass over the indices (32 KB of LDS) */
+#define GLARE_VQ_USAGE_SPAN 4096        /* tokens of a group one workgroup histograms, at least (n_tokens / 64 beyond 64 spans) */
+#define GLARE_VQ_USAGE_MAX_CODES 1048576
+size_t glare_vq_usage_workspace_bytes(int groups, long long n_tokens, int n_codes);
+int glare_vq_usage_i64(const long long* idx_i64, int groups, long long n_tokens, int n_codes, long long* counts,
+                       long long* out_of_range, long long* total, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+int glare_vq_usage_stats(const long long* counts, int rows, int n_codes, long long* tokens, long long* active, double* entropy,
+                         double* perplexity, glare_stream_t stream);
+
 /* ---- a1/a6/a8: im2col-free direct convolution on bf16 MFMA ----------------------------------
  * Replaces torch.nn.Conv2d / F.conv2d for the 3x3 and 1x1 convolutions of the VQGAN
  * encoder/decoder, AttnBlock projections, WarpBlock.offset, DCNv2Pack.conv_offset and the flow
