@@ -8,6 +8,7 @@ code/train_stage3.py:138-300 over models/base_model.py:46-83 and models/lr_sched
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --vgg16 vgg16.pth --lpips-heads vgg.pth [--gan]
     python -m glare_amd.fit stage3 --root LOLdataset --out run --net-g stage2_G.pth --net-vq vqgan.pkl --vgg16 vgg16.pth
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-usage        (log the codebook's use; glare_amd.evaluate stage1 scores the run)
+    python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-restart 100  (every 100 steps, re-seed the codes nothing selected)
 
 Stage 1 trains the VQGAN prior itself (VQModel_arch.py:98-101, 148-157) on the ground-truth half of the pairs and writes
 <out>/models/<iter>_VQ.pth under the reference's VQModel key names: what `--net-vq` of stages 2 and 3, `evaluate` and `enhance` load.
@@ -304,6 +305,18 @@ def check_perceptual_options(stage, vgg16=None, lpips_heads=None, perceptual_wei
         raise ValueError("--perceptual-weight needs --vgg16 and --lpips-heads: without them stage1 has no perceptual term to weigh")
 
 
+def check_restart_options(stage, codebook_restart=0, restart_threshold=None):
+    """The refusals of --codebook-restart / --restart-threshold: ValueError with the reason, before anything is built."""
+    if stage != "stage1" and (codebook_restart or restart_threshold is not None):
+        raise ValueError(CODEBOOK_RESTART_REFUSAL)
+    if codebook_restart is not None and int(codebook_restart) < 0:
+        raise ValueError("--codebook-restart takes the number of steps between two restarts (0: off), not %d" % codebook_restart)
+    if restart_threshold is not None and not codebook_restart:
+        raise ValueError("--restart-threshold needs --codebook-restart: without it no code is ever re-seeded")
+    if restart_threshold is not None and int(restart_threshold) < 0:
+        raise ValueError("--restart-threshold is a token count (a code is dead at <= that many selections in a window), not %d" % restart_threshold)
+
+
 def build_perceptual(stage, device, vgg16=None, lpips_heads=None):
     """The frozen loss network of the stage from the user's files (losses.load_vgg16, strict; `.loaded_keys`: what it loaded), or None
     without --vgg16."""
@@ -317,12 +330,12 @@ def build_perceptual(stage, device, vgg16=None, lpips_heads=None):
 
 
 def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16", gan=False, net_d=None, vgg16=None,
-                  lpips_heads=None, perceptual_weight=None, codebook_usage=False):
+                  lpips_heads=None, perceptual_weight=None, codebook_usage=False, codebook_restart=0, restart_threshold=None):
     """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer.  gan (stage 1 only): with the
     patch discriminator (taming's initialisation under the run's seed, or the `_D.pth` file net_d).  vgg16 / lpips_heads: the weight
     files of the perceptual term (stage 1: LPIPS, both files; stage 3: the VGG16-feature loss, the backbone alone); perceptual_weight:
     stage 1's factor on it (default 1.0).  The loss network is frozen and is written to no checkpoint: a resumed run names the files again.
-    codebook_usage (stage 1 only): Stage1Trainer's; off, the trainer is built without the keyword."""
+    codebook_usage, codebook_restart / restart_threshold (stage 1 only): Stage1Trainer's; off, the trainer is built without the keywords."""
     from . import modules as M
 
     check_perceptual_options(stage, vgg16, lpips_heads, perceptual_weight)
@@ -334,6 +347,7 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
         raise ValueError(GAN_REFUSAL)
     if stage != "stage1" and codebook_usage:
         raise ValueError(CODEBOOK_USAGE_REFUSAL)
+    check_restart_options(stage, codebook_restart, restart_threshold)
     netG, net_hq = checkpoint.build_nets(stage, True, net_g, net_vq, options, device)
     if stage == "stage1":
         disc = None
@@ -348,7 +362,9 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
                                    disc_start=tr.get("disc_start", 10000), disc_weight=tr.get("disc_weight", 0.8),
                                    disc_factor=tr.get("disc_factor", 1.0), perceptual=perceptual,
                                    perceptual_weight=1.0 if perceptual_weight is None else float(perceptual_weight),
-                                   **({"codebook_usage": True} if codebook_usage else {}))
+                                   **({"codebook_usage": True} if codebook_usage else {}),
+                                   **({"codebook_restart": int(codebook_restart), "restart_threshold": int(restart_threshold or 0)}
+                                      if codebook_restart else {}))
     if stage == "stage2":
         return train.Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
                                    train_rrdb=bool(options["network_G"].get("train_RRDB", False)), precision=precision)
@@ -358,6 +374,8 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
 
 CODEBOOK_USAGE_REFUSAL = ("--codebook-usage is a stage1 option: stage1 is the stage that trains the codebook (stages 2 and 3 read a frozen one; "
                           "glare_amd.evaluate stage1 reports the use of a finished prior's)")
+CODEBOOK_RESTART_REFUSAL = ("--codebook-restart / --restart-threshold are stage1 options: stage1 is the stage that trains the codebook (stages 2 "
+                            "and 3 read a frozen one, which has no dead codes to revive)")
 GAN_REFUSAL = "--gan is a stage1 option: the patch discriminator belongs to the VQGAN prior's objective (stages 2 and 3 train no GAN term)"
 LPIPS_REFUSAL = ("stage1's perceptual term is LPIPS and needs both files: --vgg16 (the VGG16 backbone) and --lpips-heads (the five linear "
                  "heads, taming's / the lpips package's vgg.pth); one without the other would leave half the network at its initialisation")
@@ -472,6 +490,10 @@ def parse_args(argv=None):
     ap.add_argument("--perceptual-weight", type=float, default=None, help="stage1: factor on the LPIPS term (default 1.0)")
     ap.add_argument("--codebook-usage", action="store_true", help="stage1: log codebook_active / codebook_perplexity of every step's indices, and "
                                                                    "the test split's codebook use with the closing validation")
+    ap.add_argument("--codebook-restart", type=int, default=0, metavar="P",
+                    help="stage1: every P steps, re-seed the codes that no token selected since the last restart from the step's encoder outputs")
+    ap.add_argument("--restart-threshold", type=int, default=None, metavar="T",
+                    help="--codebook-restart: a code is dead when at most T tokens selected it in the window (default 0)")
     ap.add_argument("--no-val", action="store_true", help="skip the closing validation")
     args = ap.parse_args(argv)
     if args.codebook_usage and args.stage != "stage1":
@@ -483,6 +505,7 @@ def parse_args(argv=None):
     if not args.gan and (args.disc_start is not None or args.disc_weight is not None):
         ap.error("--disc-start / --disc-weight need --gan")
     try:
+        check_restart_options(args.stage, args.codebook_restart, args.restart_threshold)
         check_perceptual_options(args.stage, args.vgg16, args.lpips_heads, args.perceptual_weight)
     except ValueError as e:
         ap.error(str(e))
@@ -521,7 +544,7 @@ def main(argv=None):
     dataset = D.DeviceLoLDataset(host_ds, device)
     trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision, gan=args.gan, net_d=net_d,
                             vgg16=args.vgg16, lpips_heads=args.lpips_heads, perceptual_weight=args.perceptual_weight,
-                            codebook_usage=args.codebook_usage)
+                            codebook_usage=args.codebook_usage, codebook_restart=args.codebook_restart, restart_threshold=args.restart_threshold)
     if args.vgg16:        # the opening line of a run with a perceptual term: which files it was built from
         print(json.dumps({"perceptual": type(trainer.perceptual).__name__, "vgg16": args.vgg16, "lpips_heads": args.lpips_heads,
                           "tensors_loaded": len(trainer.perceptual.loaded_keys)}), flush=True)

@@ -68,6 +68,7 @@ class VQModel(HipModule):
         quant2 = A.conv2d_small(zq, self.post_quant_conv.weight, self.post_quant_conv.bias, layout="nhwc", out_f32=True)
         xrec, _ = self.decoder.train_nhwc(quant2)
         self.last_indices = idx
+        self.last_latent = z.detach().reshape(-1, z.shape[-1])        # fp32 [N, 3]: what the codebook layer was fed (Stage1Trainer's restart)
         return xrec, qloss, idx
 
     def forward(self, input):  # VQModel_arch.py:98-101

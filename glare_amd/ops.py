@@ -62,6 +62,29 @@ def vq_usage_stats(counts):
     return tuple(t[0] for t in out) if counts.dim() == 1 else out
 
 
+def vq_restart(window, z_tokens, codebook, offset, threshold=0, exp_avg=None, exp_avg_sq=None):
+    """Re-seeds, IN PLACE, the codes of `codebook` [K,3] fp32 that the histogram `window` (int64 [K], vq_usage's `total`) shows no more than
+    `threshold` tokens selected: the j-th such code becomes token (offset + j * (N // R)) mod N of z_tokens [N,3] fp32, R = min(dead codes, N),
+    and its rows of exp_avg / exp_avg_sq (both or neither) become +0.0; a token with an inf / NaN re-seeds nothing; `window` is zeroed.
+    -> (n_dead, n_restarted), 0-d int64 device tensors.  No host read, no atomics, the same bits on every run (csrc/vq_restart.hip)."""
+    require_cuda(window, z_tokens, codebook, exp_avg, exp_avg_sq)
+    assert (exp_avg is None) == (exp_avg_sq is None), "exp_avg and exp_avg_sq: both or neither"
+    k, dim = codebook.shape
+    assert window.dtype == torch.int64 and tuple(window.shape) == (k,) and window.is_contiguous(), (window.dtype, tuple(window.shape))
+    assert z_tokens.dtype == torch.float32 and z_tokens.dim() == 2 and z_tokens.shape[1] == dim and z_tokens.shape[0] > 0, tuple(z_tokens.shape)
+    for t in (codebook, exp_avg, exp_avg_sq):       # written in place: a copy would take the update with it
+        assert t is None or (t.dtype == torch.float32 and tuple(t.shape) == (k, dim) and t.is_contiguous() and t.device == window.device)
+    z_tokens = z_tokens.contiguous()
+    lib = _lib.main_lib()
+    nws = lib.glare_vq_restart_workspace_bytes(k)
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=window.device)
+    out = torch.empty(2, dtype=torch.int64, device=window.device)
+    check(lib.glare_vq_restart_f32(ptr(window), int(threshold), ptr(z_tokens), z_tokens.shape[0], k, dim, int(offset), ptr(codebook),
+                                   ptr(exp_avg), ptr(exp_avg_sq), out.data_ptr(), out.data_ptr() + 8, ptr(ws), nws, stream_handle()),
+          "glare_vq_restart_f32")
+    return out[0], out[1]
+
+
 # ---- convolution --------------------------------------------------------------------------------
 # Every constant and both structs of this section are read from include/glare_hip.h (_lib.constants(), _lib.structs()).
 _K = _lib.constants()

@@ -276,6 +276,22 @@ STAGE1_NEVER_USED = ("conv_semantic.",)
 DISC_KEY = "discriminator"   # stage 1 with a discriminator: its Adam and GradScaler state dicts, one more top-level key of a `.state` file
 GAN_TERMS = ("g_loss", "d_weight", "d_loss")
 USAGE_TERMS = ("codebook_active", "codebook_perplexity")      # Stage1Trainer(codebook_usage=True)
+RESTART_KEY = "codebook_restart"   # Stage1Trainer(codebook_restart=P): {"window": int64 [K], "every": P, "threshold": T}, one more key of a `.state` file
+RESTART_TERMS = ("codebook_restarted",)
+RESTART_OFFSET_STEP = 7919         # the r-th restart of a run takes its tokens from offset r * 7919 (a prime: successive restarts start apart)
+
+
+def exchange_restart_inputs(window, z):
+    """World size > 1: what a restart step needs for every rank to re-seed the same rows with the same values -- `window` (int64 [K],
+    each rank's own histogram) is all-reduced with SUM in place, `z` ([N, 3] latents) becomes rank 0's.  -> (window, z).  The identity at
+    world size 1 or without a process group.  Plain torch.distributed calls (they take CPU tensors under gloo); with more than one rank
+    this has run under gloo only."""
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return window, z
+    dist.all_reduce(window)                      # SUM
+    z = z.contiguous()
+    dist.broadcast(z, src=0)
+    return window, z
 
 
 def two_group_adam(params, lr, weight_decay, never_used=(), second=(), second_lr=None, second_weight_decay=0.0, betas=(0.9, 0.999),
@@ -496,15 +512,30 @@ class Stage1Trainer(Trainer):
 
     def __init__(self, net, lr_G=1e-4, weight_decay_G=0.0, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0,
                  device_state=False, precision="fp16", discriminator=None, disc_start=10000, disc_weight=0.8, disc_factor=1.0,
-                 codebook_usage=False):
+                 codebook_usage=False, codebook_restart=0, restart_threshold=0):
         """lr_G: a starting point, not a tuned value (the reference sets `self.learning_rate` from a config it does not ship).
         discriminator: an NLayerDiscriminator on the net's device, or None (no GAN term: the step and every file are what they were);
         disc_start / disc_weight / disc_factor: taming's defaults for the VQGAN configs.
         codebook_usage: every step also puts `codebook_active` (int64: the distinct codes the step's indices select) and
         `codebook_perplexity` (fp64, quantize.py:83-85) of that forward pass into last_terms -- three small launches (csrc/vq_usage.hip), no
         host synchronisation; off (the default), the step launches and records what it always did.  Usage is not state: nothing of it
-        is written to a `.state` file."""
+        is written to a `.state` file.
+        codebook_restart: P > 0 revives dead codes every P steps (csrc/vq_restart.hip); 0 (the default) is off, and the step then launches
+        and records exactly what it always did.  A code no token selects gets dE = 0 and never moves again -- at the reference's
+        initialisation (uniform(-1/8192, 1/8192)) that is most of the codebook.  On: every step adds its indices' histogram to a persistent
+        int64 [K] window (`restart_window`; the one ops.vq_usage call codebook_usage makes too), and after `opt.step()` of every step whose
+        new global_step is a multiple of P, the codes with window count <= restart_threshold are overwritten, in ascending order, with evenly
+        strided rows of this step's `net.last_latent`, starting at token (global_step // P) * 7919; their Adam moments are zeroed, the
+        window restarts from zero, and `last_terms["codebook_restarted"]` holds the number of rows written (a device zero on the other
+        steps).  All of it on the device: no count is read back.  The restart depends on no gradient, so a step the GradScaler skipped
+        restarts all the same.  Adam's step count is ONE device scalar shared by every parameter: a re-seeded row starts again from zero
+        moments but under the run's global bias correction (1 - beta^t, t the run's step count), not a fresh t = 1 -- late in a
+        run its first update is about (1 - beta1) / sqrt(1 - beta2) lr (1.58 lr at this stage's betas) where a new parameter's is lr.  The window is state: it travels in the `.state` file with P
+        and the threshold, and a resume under other values is refused.  World size > 1: exchange_restart_inputs."""
         self.codebook_usage = bool(codebook_usage)
+        self.codebook_restart, self.restart_threshold = int(codebook_restart), int(restart_threshold)
+        assert self.codebook_restart >= 0 and self.restart_threshold >= 0, (codebook_restart, restart_threshold)
+        self.restart_window = None                   # off: ops.vq_usage is handed no total, as ever
         self.codebook_weight, self.perceptual, self.perceptual_weight = float(codebook_weight), perceptual, float(perceptual_weight)
         for p in net.parameters():
             p.requires_grad_(True)
@@ -516,6 +547,19 @@ class Stage1Trainer(Trainer):
         self.discriminator, self.opt_d = discriminator, None
         self.disc_start, self.disc_weight, self.disc_factor = int(disc_start), float(disc_weight), float(disc_factor)
         self.global_step = 0                         # Lightning's global_step: steps taken so far (on_resume restores it)
+        if self.codebook_restart:
+            # the parameters are views of FlatGroup.w: the embedding's rows of w, exp_avg and exp_avg_sq sit at one static offset
+            E, g0, off = net.quantize.embedding.weight, self.opt.groups[0], 0
+            for p in g0.params:
+                if p is E:
+                    break
+                off += p.numel()
+            else:
+                raise RuntimeError("the codebook is not a parameter of the optimizer's first group")
+            self._restart_rows = tuple(t[off:off + E.numel()].view(E.shape) for t in (g0.w, g0.m, g0.v))
+            assert self._restart_rows[0].data_ptr() == E.data_ptr()
+            self.restart_window = torch.zeros(E.shape[0], dtype=torch.int64, device=E.device)
+            self._restart_none = torch.zeros((), dtype=torch.int64, device=E.device)
         if discriminator is not None:
             discriminator.train()
             for p in discriminator.parameters():
@@ -529,28 +573,62 @@ class Stage1Trainer(Trainer):
         return {} if self.discriminator is None else {"D": self.discriminator}
 
     def extra_state(self):
-        """D's Adam and GradScaler state travel as one more key of the `.state` file."""
-        if self.discriminator is None:
-            return {}
-        return {DISC_KEY: {"optimizer": checkpoint.adam_state_dict(self.opt_d), "scaler": self.opt_d.scaler_state_dict()}}
+        """D's Adam and GradScaler state, and the restart's window with its two settings, travel as further keys of the `.state` file."""
+        extra = {}
+        if self.discriminator is not None:
+            extra[DISC_KEY] = {"optimizer": checkpoint.adam_state_dict(self.opt_d), "scaler": self.opt_d.scaler_state_dict()}
+        if self.codebook_restart:
+            extra[RESTART_KEY] = {"window": self.restart_window.cpu().clone(), "every": self.codebook_restart,
+                                  "threshold": self.restart_threshold}
+        return extra
 
     def load_extra_state(self, state):
         if self.discriminator is not None:
             assert DISC_KEY in state, "--gan: the .state file carries no discriminator optimizer (it was written without --gan)"
             checkpoint.load_adam_state_dict(self.opt_d, state[DISC_KEY]["optimizer"])
             self.opt_d.load_scaler_state_dict(state[DISC_KEY]["scaler"])
+        saved = state.get(RESTART_KEY)
+        if self.codebook_restart:
+            assert saved is not None, ("--codebook-restart: the .state file carries no restart window (it was written without "
+                                       "--codebook-restart)")
+            assert (int(saved["every"]), int(saved["threshold"])) == (self.codebook_restart, self.restart_threshold), (
+                "--codebook-restart: the .state file was written with --codebook-restart %d --restart-threshold %d and this run has %d and %d: "
+                "the window would be read against another rule partway through; name the same values again"
+                % (saved["every"], saved["threshold"], self.codebook_restart, self.restart_threshold))
+            self.restart_window.copy_(saved["window"])
+        else:
+            assert saved is None, ("the .state file carries a restart window (it was written with --codebook-restart %d) and this run has "
+                                   "no --codebook-restart: name it again" % saved["every"])
 
     def on_resume(self, step):
-        self.global_step = step                      # what `disc_start` is compared with
+        self.global_step = step                      # what `disc_start` and the restart's period are compared with
 
     def log_terms(self):
-        return (GAN_TERMS if self.discriminator is not None else ()) + super().log_terms() + (USAGE_TERMS if self.codebook_usage else ())
+        return ((GAN_TERMS if self.discriminator is not None else ()) + super().log_terms() + (USAGE_TERMS if self.codebook_usage else ())
+                + (RESTART_TERMS if self.codebook_restart else ()))
 
     def _usage_terms(self, idx):
-        """{codebook_active, codebook_perplexity} of one forward pass's indices, device tensors."""
-        counts, _, _ = ops.vq_usage(idx, self.net.quantize.n_e)
+        """{codebook_active, codebook_perplexity} of one forward pass's indices, device tensors.  With the restart on, the same
+        histogram call adds the step's counts to its window."""
+        counts, _, _ = ops.vq_usage(idx, self.net.quantize.n_e, total=self.restart_window)
         _, active, _, perplexity = ops.vq_usage_stats(counts)
         return {"codebook_active": active[0], "codebook_perplexity": perplexity[0]}
+
+    def _codebook_terms(self, idx):
+        """What follows `opt.step()` for the codebook's bookkeeping: the usage terms, the restart's window and, on its steps, the restart
+        itself.  Both options off: nothing is launched and {} comes back."""
+        terms = self._usage_terms(idx) if self.codebook_usage else {}
+        if not self.codebook_restart:
+            return terms
+        if not self.codebook_usage:
+            ops.vq_usage(idx, self.net.quantize.n_e, total=self.restart_window)
+        terms["codebook_restarted"] = self._restart_none
+        if self.global_step % self.codebook_restart == 0:          # global_step: already this step's new count
+            w, m, v = self._restart_rows
+            window, z = exchange_restart_inputs(self.restart_window, self.net.last_latent)
+            offset = (self.global_step // self.codebook_restart) * RESTART_OFFSET_STEP
+            _, terms["codebook_restarted"] = ops.vq_restart(window, z, w, offset, self.restart_threshold, m, v)
+        return terms
 
     def invalidate(self):
         self.net.invalidate()
@@ -575,8 +653,7 @@ class Stage1Trainer(Trainer):
                 self.opt.scale_loss(loss).backward()
             self.opt.step()
         self.net.invalidate()                        # packed inference weights are stale now
-        if self.codebook_usage:
-            self.last_terms.update(self._usage_terms(idx))
+        self.last_terms.update(self._codebook_terms(idx))     # (the search reads embedding.weight itself: nothing packed goes stale)
         if self.discriminator is not None:           # before disc_start: f = 0, nothing of D launched, its parameters and optimizer untouched
             self.last_terms.update(g_loss=self._zero, d_weight=self._zero, d_loss=self._zero)
         return loss.detach()
@@ -626,8 +703,7 @@ class Stage1Trainer(Trainer):
         loss = nll.detach() + d_weight * f * g_loss.detach() + cb.detach()
         terms["codebook_loss"] = cb
         terms.update(g_loss=g_loss.detach(), d_weight=d_weight, d_loss=d_loss.detach())
-        if self.codebook_usage:
-            terms.update(self._usage_terms(idx))
+        terms.update(self._codebook_terms(idx))
         self.last_terms = terms
         return loss
 

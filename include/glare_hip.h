@@ -105,6 +105,31 @@ int glare_vq_usage_i64(const long long* idx_i64, int groups, long long n_tokens,
 int glare_vq_usage_stats(const long long* counts, int rows, int n_codes, long long* tokens, long long* active, double* entropy,
                          double* perplexity, glare_stream_t stream);
 
+/* ---- a5, restart: re-seed the codes nothing selected from current encoder outputs (csrc/vq_restart.hip) --------------------
+ * The codebook trains through dE alone, and dE is exactly 0 for a code no token selected (above): such a code never moves again.  The
+ * fix of VQ-VAE / VQGAN training code: every so many steps the codes of a window's histogram (glare_vq_usage_i64's `total`) that
+ * nothing selected are overwritten with latents of the current batch.  (The reference's EMAVectorQuantizer is not this: its constructor
+ * reads names it never defines, quantize.py:365-366.)
+ *   dead = {k : window_counts[k] <= threshold} in ascending order d_0 < d_1 < ...;  D = |dead|;  R = min(D, n_tokens)
+ *   R > 0: stride = n_tokens / R (integer);  t_j = (offset + j * stride) mod n_tokens, j < R -- distinct, as R * stride <= n_tokens;
+ *          a negative offset is taken by the true modulo
+ *   j < R and the three components of z_tokens[t_j] finite: codebook[d_j] = z_tokens[t_j] (a bit copy), exp_avg[d_j] = exp_avg_sq[d_j] = +0.0
+ *   a source token with an inf / NaN re-seeds nothing and is not counted; dead codes of rank >= R wait for the next window; a live
+ *   code's row and moments keep their bits
+ *   n_dead[0] = D, n_restarted[0] = rows written, window_counts all zero on return
+ * window_counts [n_codes] int64 in / zeroed; z_tokens [n_tokens][3] fp32; codebook, exp_avg, exp_avg_sq [n_codes][3] fp32 in place
+ * (the two moments both given or both NULL); n_dead, n_restarted [1] int64.  D, R and stride stay on the device: four launches, no host
+ * read.  The rank of a dead code is a three-level integer scan -- a wave64 ballot and popcount, a fixed LDS scan of the workgroup's wave
+ * totals, one launch over the workgroup totals -- exact and the same bits on every run; no global atomics.  The only data-dependent
+ * addresses are z_tokens[t_j], t_j an unsigned remainder of n_tokens, and the rows d_j, the scan's own loop indices behind k < n_codes.
+ * workspace: glare_vq_restart_workspace_bytes(n_codes) bytes, 8-byte aligned (0: not a size the kernels take).
+ * GLARE_ERR_INVALID: a null pointer (the two moments excepted when both are null), exactly one moment null, a non-positive size, a
+ * workspace that is not 8-byte aligned; GLARE_ERR_UNSUPPORTED: dim != 3, n_codes > GLARE_VQ_USAGE_MAX_CODES; GLARE_ERR_WORKSPACE as elsewhere -- all before any launch. */
+size_t glare_vq_restart_workspace_bytes(int n_codes);
+int glare_vq_restart_f32(long long* window_counts, long long threshold, const float* z_tokens, long long n_tokens, int n_codes, int dim,
+                         long long offset, float* codebook, float* exp_avg, float* exp_avg_sq, long long* n_dead, long long* n_restarted,
+                         void* workspace, size_t workspace_bytes, glare_stream_t stream);
+
 /* ---- a1/a6/a8: im2col-free direct convolution on bf16 MFMA ----------------------------------
  * Replaces torch.nn.Conv2d / F.conv2d for the 3x3 and 1x1 convolutions of the VQGAN
  * encoder/decoder, AttnBlock projections, WarpBlock.offset, DCNv2Pack.conv_offset and the flow
