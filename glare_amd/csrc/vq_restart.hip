@@ -12,6 +12,7 @@
 //   finish  ONE workgroup adds the per-workgroup counts in a fixed order: n_restarted[0]
 // Integers only, so every sum is exact and the same on every run; no atomics of any kind.  The data-dependent addresses: z[t], t an
 // UNSIGNED remainder of N whatever the header holds, and row k behind k < K -- the scan's loop index, not a loaded value.
+// glare_vq_restart_ema_f32: the same launches for an EMA codebook -- a written row is also its embed_avg row, cluster_size[k] = seed_size.
 // Rows are copied as 32-bit words: a bit copy.  Compiled with -ffp-contract=off like the other vq*.hip (no float arithmetic here at all).
 #include "common.h"
 
@@ -91,7 +92,8 @@ __global__ __launch_bounds__(VR_THREADS) void vq_restart_apply_kernel(long long*
                                                                       const unsigned* __restrict__ group_off,
                                                                       const long long* __restrict__ header, uint32_t* __restrict__ codebook,
                                                                       uint32_t* __restrict__ exp_avg, uint32_t* __restrict__ exp_avg_sq,
-                                                                      unsigned* __restrict__ group_written) {
+                                                                      uint32_t* __restrict__ embed_avg, float* __restrict__ cluster_size,
+                                                                      float seed_size, unsigned* __restrict__ group_written) {
   __shared__ unsigned wave_tot[VR_WAVES];
   const int k = (int)(blockIdx.x * VR_THREADS + threadIdx.x);
   unsigned total;
@@ -112,6 +114,12 @@ __global__ __launch_bounds__(VR_THREADS) void vq_restart_apply_kernel(long long*
       if (exp_avg) {
         exp_avg[row] = exp_avg[row + 1] = exp_avg[row + 2] = 0u;
         exp_avg_sq[row] = exp_avg_sq[row + 1] = exp_avg_sq[row + 2] = 0u;
+      }
+      if (embed_avg) {                                // the EMA form: the running sum restarts at the row, its weight at seed_size
+        embed_avg[row] = a;
+        embed_avg[row + 1] = b;
+        embed_avg[row + 2] = c;
+        cluster_size[k] = seed_size;
       }
       wrote = true;
     }
@@ -151,12 +159,12 @@ extern "C" size_t glare_vq_restart_workspace_bytes(int n_codes) {
   return VR_HEADER * sizeof(long long) + 3 * (size_t)cdiv(n_codes, VR_THREADS) * sizeof(unsigned);
 }
 
-extern "C" int glare_vq_restart_f32(long long* window_counts, long long threshold, const float* z_tokens, long long n_tokens, int n_codes,
-                                    int dim, long long offset, float* codebook, float* exp_avg, float* exp_avg_sq, long long* n_dead,
-                                    long long* n_restarted, void* workspace, size_t workspace_bytes, glare_stream_t stream) {
-  if (n_tokens <= 0 || n_codes <= 0 || dim <= 0) return GLARE_ERR_INVALID;
-  if (!window_counts || !z_tokens || !codebook || !n_dead || !n_restarted || !workspace) return GLARE_ERR_INVALID;
-  if ((exp_avg == nullptr) != (exp_avg_sq == nullptr)) return GLARE_ERR_INVALID;
+namespace {
+
+// Both entries: the same four launches; embed_avg / cluster_size are the EMA form's, exp_avg / exp_avg_sq the gradient form's.
+int restart_launch(long long* window_counts, long long threshold, const float* z_tokens, long long n_tokens, int n_codes, int dim,
+                   long long offset, float* codebook, float* exp_avg, float* exp_avg_sq, float* embed_avg, float* cluster_size,
+                   float seed_size, long long* n_dead, long long* n_restarted, void* workspace, size_t workspace_bytes, glare_stream_t stream) {
   if (((uintptr_t)workspace & 7u) != 0) return GLARE_ERR_INVALID;
   if (dim != 3 || n_codes > GLARE_VQ_USAGE_MAX_CODES) return GLARE_ERR_UNSUPPORTED;
   if (workspace_bytes < glare_vq_restart_workspace_bytes(n_codes)) return GLARE_ERR_WORKSPACE;
@@ -170,7 +178,33 @@ extern "C" int glare_vq_restart_f32(long long* window_counts, long long threshol
   hipLaunchKernelGGL(vq_restart_scan_kernel, dim3(1), dim3(VR_THREADS), 0, s, group_dead, groups, n_tokens, offset, group_off, header, n_dead);
   hipLaunchKernelGGL(vq_restart_apply_kernel, dim3((unsigned)groups), dim3(VR_THREADS), 0, s, window_counts, threshold,
                      reinterpret_cast<const uint32_t*>(z_tokens), n_tokens, n_codes, group_off, header, reinterpret_cast<uint32_t*>(codebook),
-                     reinterpret_cast<uint32_t*>(exp_avg), reinterpret_cast<uint32_t*>(exp_avg_sq), group_written);
+                     reinterpret_cast<uint32_t*>(exp_avg), reinterpret_cast<uint32_t*>(exp_avg_sq), reinterpret_cast<uint32_t*>(embed_avg),
+                     cluster_size, seed_size, group_written);
   hipLaunchKernelGGL(vq_restart_finish_kernel, dim3(1), dim3(VR_THREADS), 0, s, group_written, groups, n_restarted);
   return glare_launch_status();
+}
+
+}  // namespace
+
+extern "C" int glare_vq_restart_f32(long long* window_counts, long long threshold, const float* z_tokens, long long n_tokens, int n_codes,
+                                    int dim, long long offset, float* codebook, float* exp_avg, float* exp_avg_sq, long long* n_dead,
+                                    long long* n_restarted, void* workspace, size_t workspace_bytes, glare_stream_t stream) {
+  if (n_tokens <= 0 || n_codes <= 0 || dim <= 0) return GLARE_ERR_INVALID;
+  if (!window_counts || !z_tokens || !codebook || !n_dead || !n_restarted || !workspace) return GLARE_ERR_INVALID;
+  if ((exp_avg == nullptr) != (exp_avg_sq == nullptr)) return GLARE_ERR_INVALID;
+  return restart_launch(window_counts, threshold, z_tokens, n_tokens, n_codes, dim, offset, codebook, exp_avg, exp_avg_sq, nullptr, nullptr,
+                        0.f, n_dead, n_restarted, workspace, workspace_bytes, stream);
+}
+
+// The restart under an EMA codebook (csrc/vq_ema.hip): the same dead codes, ranking and source tokens; a written row also becomes its
+// embed_avg row (a bit copy) and cluster_size[k] = seed_size.  No Adam moments: the codebook is no Adam parameter there.
+extern "C" int glare_vq_restart_ema_f32(long long* window_counts, long long threshold, const float* z_tokens, long long n_tokens, int n_codes,
+                                        int dim, long long offset, float seed_size, float* codebook, float* embed_avg, float* cluster_size,
+                                        long long* n_dead, long long* n_restarted, void* workspace, size_t workspace_bytes,
+                                        glare_stream_t stream) {
+  if (n_tokens <= 0 || n_codes <= 0 || dim <= 0) return GLARE_ERR_INVALID;
+  if (!window_counts || !z_tokens || !codebook || !embed_avg || !cluster_size || !n_dead || !n_restarted || !workspace) return GLARE_ERR_INVALID;
+  if (!(seed_size >= 0.f && seed_size <= 3.0e38f)) return GLARE_ERR_INVALID;       // finite and not negative (a NaN fails both)
+  return restart_launch(window_counts, threshold, z_tokens, n_tokens, n_codes, dim, offset, codebook, nullptr, nullptr, embed_avg,
+                        cluster_size, seed_size, n_dead, n_restarted, workspace, workspace_bytes, stream);
 }

@@ -9,6 +9,7 @@ code/train_stage3.py:138-300 over models/base_model.py:46-83 and models/lr_sched
     python -m glare_amd.fit stage3 --root LOLdataset --out run --net-g stage2_G.pth --net-vq vqgan.pkl --vgg16 vgg16.pth
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-usage        (log the codebook's use; glare_amd.evaluate stage1 scores the run)
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-restart 100  (every 100 steps, re-seed the codes nothing selected)
+    python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-ema 0.99 --codebook-restart 100   (an EMA codebook, no gradient)
 
 Stage 1 trains the VQGAN prior itself (VQModel_arch.py:98-101, 148-157) on the ground-truth half of the pairs and writes
 <out>/models/<iter>_VQ.pth under the reference's VQModel key names: what `--net-vq` of stages 2 and 3, `evaluate` and `enhance` load.
@@ -317,6 +318,18 @@ def check_restart_options(stage, codebook_restart=0, restart_threshold=None):
         raise ValueError("--restart-threshold is a token count (a code is dead at <= that many selections in a window), not %d" % restart_threshold)
 
 
+def check_ema_options(stage, codebook_ema=None, ema_eps=None):
+    """The refusals of --codebook-ema / --ema-eps: ValueError with the reason, before anything is built."""
+    if stage != "stage1" and (codebook_ema is not None or ema_eps is not None):
+        raise ValueError(CODEBOOK_EMA_REFUSAL)
+    if codebook_ema is not None and not 0.0 < float(codebook_ema) < 1.0:
+        raise ValueError("--codebook-ema takes the decay of the moving average, a number in (0, 1) such as 0.99, not %r" % (codebook_ema,))
+    if ema_eps is not None and codebook_ema is None:
+        raise ValueError("--ema-eps needs --codebook-ema: without it the codebook follows its gradient and no cluster size is smoothed")
+    if ema_eps is not None and not float(ema_eps) >= 0.0:
+        raise ValueError("--ema-eps is the smoothing added to every cluster size (default 1e-5), not %r" % (ema_eps,))
+
+
 def build_perceptual(stage, device, vgg16=None, lpips_heads=None):
     """The frozen loss network of the stage from the user's files (losses.load_vgg16, strict; `.loaded_keys`: what it loaded), or None
     without --vgg16."""
@@ -330,12 +343,14 @@ def build_perceptual(stage, device, vgg16=None, lpips_heads=None):
 
 
 def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16", gan=False, net_d=None, vgg16=None,
-                  lpips_heads=None, perceptual_weight=None, codebook_usage=False, codebook_restart=0, restart_threshold=None):
+                  lpips_heads=None, perceptual_weight=None, codebook_usage=False, codebook_restart=0, restart_threshold=None,
+                  codebook_ema=None, ema_eps=None):
     """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer.  gan (stage 1 only): with the
     patch discriminator (taming's initialisation under the run's seed, or the `_D.pth` file net_d).  vgg16 / lpips_heads: the weight
     files of the perceptual term (stage 1: LPIPS, both files; stage 3: the VGG16-feature loss, the backbone alone); perceptual_weight:
     stage 1's factor on it (default 1.0).  The loss network is frozen and is written to no checkpoint: a resumed run names the files again.
-    codebook_usage, codebook_restart / restart_threshold (stage 1 only): Stage1Trainer's; off, the trainer is built without the keywords."""
+    codebook_usage, codebook_restart / restart_threshold, codebook_ema / ema_eps (stage 1 only): Stage1Trainer's; off, the trainer is built
+    without the keywords."""
     from . import modules as M
 
     check_perceptual_options(stage, vgg16, lpips_heads, perceptual_weight)
@@ -348,6 +363,7 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
     if stage != "stage1" and codebook_usage:
         raise ValueError(CODEBOOK_USAGE_REFUSAL)
     check_restart_options(stage, codebook_restart, restart_threshold)
+    check_ema_options(stage, codebook_ema, ema_eps)
     netG, net_hq = checkpoint.build_nets(stage, True, net_g, net_vq, options, device)
     if stage == "stage1":
         disc = None
@@ -364,7 +380,9 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
                                    perceptual_weight=1.0 if perceptual_weight is None else float(perceptual_weight),
                                    **({"codebook_usage": True} if codebook_usage else {}),
                                    **({"codebook_restart": int(codebook_restart), "restart_threshold": int(restart_threshold or 0)}
-                                      if codebook_restart else {}))
+                                      if codebook_restart else {}),
+                                   **({"codebook_ema": float(codebook_ema), "ema_eps": 1e-5 if ema_eps is None else float(ema_eps)}
+                                      if codebook_ema is not None else {}))
     if stage == "stage2":
         return train.Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
                                    train_rrdb=bool(options["network_G"].get("train_RRDB", False)), precision=precision)
@@ -376,6 +394,8 @@ CODEBOOK_USAGE_REFUSAL = ("--codebook-usage is a stage1 option: stage1 is the st
                           "glare_amd.evaluate stage1 reports the use of a finished prior's)")
 CODEBOOK_RESTART_REFUSAL = ("--codebook-restart / --restart-threshold are stage1 options: stage1 is the stage that trains the codebook (stages 2 "
                             "and 3 read a frozen one, which has no dead codes to revive)")
+CODEBOOK_EMA_REFUSAL = ("--codebook-ema / --ema-eps are stage1 options: stage1 is the stage that trains the codebook (stages 2 and 3 read a "
+                        "frozen one, which nothing updates)")
 GAN_REFUSAL = "--gan is a stage1 option: the patch discriminator belongs to the VQGAN prior's objective (stages 2 and 3 train no GAN term)"
 LPIPS_REFUSAL = ("stage1's perceptual term is LPIPS and needs both files: --vgg16 (the VGG16 backbone) and --lpips-heads (the five linear "
                  "heads, taming's / the lpips package's vgg.pth); one without the other would leave half the network at its initialisation")
@@ -494,6 +514,10 @@ def parse_args(argv=None):
                     help="stage1: every P steps, re-seed the codes that no token selected since the last restart from the step's encoder outputs")
     ap.add_argument("--restart-threshold", type=int, default=None, metavar="T",
                     help="--codebook-restart: a code is dead when at most T tokens selected it in the window (default 0)")
+    ap.add_argument("--codebook-ema", type=float, default=None, metavar="DECAY",
+                    help="stage1: move the codebook by an exponential moving average of the latents that select each code (decay in (0, 1), "
+                         "e.g. 0.99) instead of its gradient; use with --codebook-restart, a code nothing selects is thrown far away")
+    ap.add_argument("--ema-eps", type=float, default=None, metavar="EPS", help="--codebook-ema: the smoothing of the cluster sizes (default 1e-5)")
     ap.add_argument("--no-val", action="store_true", help="skip the closing validation")
     args = ap.parse_args(argv)
     if args.codebook_usage and args.stage != "stage1":
@@ -506,6 +530,7 @@ def parse_args(argv=None):
         ap.error("--disc-start / --disc-weight need --gan")
     try:
         check_restart_options(args.stage, args.codebook_restart, args.restart_threshold)
+        check_ema_options(args.stage, args.codebook_ema, args.ema_eps)
         check_perceptual_options(args.stage, args.vgg16, args.lpips_heads, args.perceptual_weight)
     except ValueError as e:
         ap.error(str(e))
@@ -544,7 +569,8 @@ def main(argv=None):
     dataset = D.DeviceLoLDataset(host_ds, device)
     trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision, gan=args.gan, net_d=net_d,
                             vgg16=args.vgg16, lpips_heads=args.lpips_heads, perceptual_weight=args.perceptual_weight,
-                            codebook_usage=args.codebook_usage, codebook_restart=args.codebook_restart, restart_threshold=args.restart_threshold)
+                            codebook_usage=args.codebook_usage, codebook_restart=args.codebook_restart, restart_threshold=args.restart_threshold,
+                            codebook_ema=args.codebook_ema, ema_eps=args.ema_eps)
     if args.vgg16:        # the opening line of a run with a perceptual term: which files it was built from
         print(json.dumps({"perceptual": type(trainer.perceptual).__name__, "vgg16": args.vgg16, "lpips_heads": args.lpips_heads,
                           "tensors_loaded": len(trainer.perceptual.loaded_keys)}), flush=True)

@@ -63,12 +63,12 @@ class VQModel(HipModule):
         q = self.quantize
         h, _ = self.encoder.train_nhwc(x_nchw)
         z = A.conv2d_small(h, self.quant_conv.weight, self.quant_conv.bias, layout="nhwc", out_f32=True)
-        w_z, w_e = (1.0, q.beta) if q.legacy else (q.beta, 1.0)
+        w_z, w_e = q.loss_weights()
         zq, qloss, idx = A.vq_straight_through(z, q.embedding.weight, w_z, w_e)
         quant2 = A.conv2d_small(zq, self.post_quant_conv.weight, self.post_quant_conv.bias, layout="nhwc", out_f32=True)
         xrec, _ = self.decoder.train_nhwc(quant2)
         self.last_indices = idx
-        self.last_latent = z.detach().reshape(-1, z.shape[-1])        # fp32 [N, 3]: what the codebook layer was fed (Stage1Trainer's restart)
+        self.last_latent = z.detach().reshape(-1, z.shape[-1])        # fp32 [N, 3]: what the codebook layer was fed (Stage1Trainer's restart and EMA update)
         return xrec, qloss, idx
 
     def forward(self, input):  # VQModel_arch.py:98-101

@@ -22,6 +22,14 @@ class VectorQuantizer2(HipModule):
         self.embedding = nn.Embedding(n_e, e_dim)
         self.embedding.weight.data.uniform_(-1.0 / n_e, 1.0 / n_e)
         self.remap, self.re_embed, self.sane_index_shape = None, n_e, sane_index_shape
+        self.ema_update = False     # Stage1Trainer(codebook_ema=d): the codebook follows an EMA of the latents, not a gradient
+
+    def loss_weights(self):
+        """(w_z, w_e) of loss = w_z mean((z_q.detach() - z)^2) + w_e mean((z_q - z.detach())^2): quantize.py:290-295, and under an EMA
+        codebook the commitment term alone, beta mean((z_q.detach() - z)^2) (EMAVectorQuantizer.forward, quantize.py:437)."""
+        if self.ema_update:
+            return (self.beta, 0.0)
+        return (1.0, self.beta) if self.legacy else (self.beta, 1.0)
 
     def quantize_tokens(self, tokens):
         """tokens fp32 [N, e_dim] (NHWC flattening) -> (idx int64 [N], z_q fp32 [N, e_dim])."""
@@ -34,7 +42,7 @@ class VectorQuantizer2(HipModule):
         if torch.is_grad_enabled() and z.requires_grad:
             # stage-1 training (VQModel_arch.py:98-101): the same lookup with a tape -- the loss sum, the straight-through output and
             # both gradients are kernels of csrc/vq_train.hip (autograd.VQStraightThroughFn), bitwise reproducible
-            w_z, w_e = (1.0, self.beta) if self.legacy else (self.beta, 1.0)             # quantize.py:290-295
+            w_z, w_e = self.loss_weights()
             zq, loss, idx = A.vq_straight_through(A.nchw_to_nhwc_f32(z), self.embedding.weight, w_z, w_e)
             zq = A.nhwc_to_nchw(zq)
             if self.sane_index_shape:

@@ -85,6 +85,66 @@ def vq_restart(window, z_tokens, codebook, offset, threshold=0, exp_avg=None, ex
     return out[0], out[1]
 
 
+def vq_ema_stats(idx, z_tokens, n_codes):
+    """idx int64 [N] (vq_nearest's), z_tokens fp32 [N,3] -> stats fp32 [n_codes,4] = {s_k0, s_k1, s_k2, n_k}: the sum and the number of
+    the tokens that select code k (quantize.py:428, :431).  An index outside [0, n_codes) selects nothing.  N <= 2^24.  A fixed-order sum,
+    no atomics, the same bits on every run (csrc/vq_ema.hip)."""
+    require_cuda(idx, z_tokens)
+    assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.numel() > 0, (idx.dtype, tuple(idx.shape))
+    assert z_tokens.dtype == torch.float32 and z_tokens.dim() == 2 and z_tokens.shape[0] == idx.numel() and z_tokens.device == idx.device, (
+        z_tokens.dtype, tuple(z_tokens.shape))
+    idx, z_tokens = idx.contiguous(), z_tokens.contiguous()
+    n, dim = z_tokens.shape
+    lib = _lib.main_lib()
+    nws = lib.glare_vq_ema_workspace_bytes(n, int(n_codes))
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=idx.device)
+    stats = torch.empty(int(n_codes), 4, dtype=torch.float32, device=idx.device)
+    check(lib.glare_vq_ema_stats_f32(ptr(idx), ptr(z_tokens), n, int(n_codes), dim, ptr(stats), ptr(ws), nws, stream_handle()),
+          "glare_vq_ema_stats_f32")
+    return stats
+
+
+def vq_ema_update(stats, cluster_size, embed_avg, codebook, decay, eps):
+    """The EMA step of the codebook, IN PLACE on cluster_size [K], embed_avg [K,3] and codebook [K,3] (all fp32), from stats [K,4] of
+    vq_ema_stats (summed over ranks by the caller where there are several): cluster_size = d cluster_size + (1 - d) n_k, embed_avg = d
+    embed_avg + (1 - d) s_k, n = sum cluster_size, codebook[k] = embed_avg[k] / ((cluster_size[k] + eps) / (n + K eps) * n)
+    (quantize.py:345-358).  n == 0 exactly leaves the codebook as it was (the reference: 0 / 0).  decay in (0, 1), eps >= 0.  Three
+    launches, no host read, the same bits on every run (csrc/vq_ema.hip)."""
+    require_cuda(stats, cluster_size, embed_avg, codebook)
+    k, dim = codebook.shape
+    assert 0.0 < float(decay) < 1.0 and float(eps) >= 0.0, (decay, eps)
+    assert stats.dtype == torch.float32 and tuple(stats.shape) == (k, 4) and stats.device == codebook.device, (stats.dtype, tuple(stats.shape))
+    for t, shape in ((cluster_size, (k,)), (embed_avg, (k, dim)), (codebook, (k, dim))):     # written in place: a copy would take the update with it
+        assert t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == stats.device, (t.dtype, tuple(t.shape))
+    stats = stats.contiguous()
+    lib = _lib.main_lib()
+    nws = lib.glare_vq_ema_workspace_bytes(1, k)
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=stats.device)
+    check(lib.glare_vq_ema_update_f32(ptr(stats), k, dim, float(decay), float(eps), ptr(cluster_size), ptr(embed_avg), ptr(codebook), ptr(ws),
+                                      nws, stream_handle()), "glare_vq_ema_update_f32")
+
+
+def vq_restart_ema(window, z_tokens, codebook, embed_avg, cluster_size, offset, threshold=0, seed_size=1.0):
+    """vq_restart for an EMA codebook, IN PLACE: the same dead codes, ranking and source tokens; a written row of `codebook` is also
+    written to `embed_avg` [K,3] and its `cluster_size` [K] becomes seed_size.  No Adam moments.  -> (n_dead, n_restarted), 0-d int64
+    device tensors; `window` is zeroed (csrc/vq_restart.hip)."""
+    require_cuda(window, z_tokens, codebook, embed_avg, cluster_size)
+    k, dim = codebook.shape
+    assert window.dtype == torch.int64 and tuple(window.shape) == (k,) and window.is_contiguous(), (window.dtype, tuple(window.shape))
+    assert z_tokens.dtype == torch.float32 and z_tokens.dim() == 2 and z_tokens.shape[1] == dim and z_tokens.shape[0] > 0, tuple(z_tokens.shape)
+    for t, shape in ((codebook, (k, dim)), (embed_avg, (k, dim)), (cluster_size, (k,))):
+        assert t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == window.device, (t.dtype, tuple(t.shape))
+    z_tokens = z_tokens.contiguous()
+    lib = _lib.main_lib()
+    nws = lib.glare_vq_restart_workspace_bytes(k)
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=window.device)
+    out = torch.empty(2, dtype=torch.int64, device=window.device)
+    check(lib.glare_vq_restart_ema_f32(ptr(window), int(threshold), ptr(z_tokens), z_tokens.shape[0], k, dim, int(offset), float(seed_size),
+                                       ptr(codebook), ptr(embed_avg), ptr(cluster_size), out.data_ptr(), out.data_ptr() + 8, ptr(ws), nws,
+                                       stream_handle()), "glare_vq_restart_ema_f32")
+    return out[0], out[1]
+
+
 # ---- convolution --------------------------------------------------------------------------------
 # Every constant and both structs of this section are read from include/glare_hip.h (_lib.constants(), _lib.structs()).
 _K = _lib.constants()

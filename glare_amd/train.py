@@ -294,6 +294,23 @@ def exchange_restart_inputs(window, z):
     return window, z
 
 
+EMA_KEY = "codebook_ema"           # Stage1Trainer(codebook_ema=d): {"cluster_size": fp32 [K], "embed_avg": fp32 [K, 3], "decay": d, "eps": eps}
+EMA_MAX_TOKENS = 1 << 24           # the fp32 count n_k of csrc/vq_ema.hip stays exact up to here, summed over ranks too
+EMA_SEED_SIZE = 1.0                # cluster_size of a code the restart re-seeds under EMA: the mean of one token
+
+
+def exchange_ema_stats(stats, n_tokens=None):
+    """World size > 1: the ranks' per-code statistics (fp32 [K, 4] of ops.vq_ema_stats: sums and counts of this rank's n_tokens tokens) are
+    all-reduced with SUM in place, so every rank's EMA update sees the whole batch and all codebooks stay alike; world * n_tokens must
+    not pass 2^24 (the summed count is an fp32 integer).  -> stats.  The identity at world size 1 or without a process group.  A plain
+    torch.distributed call (fp32 sums in the backend's order); with more than one rank this has run under gloo only."""
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return stats
+    assert n_tokens is None or dist.get_world_size() * int(n_tokens) <= EMA_MAX_TOKENS, (dist.get_world_size(), n_tokens)
+    dist.all_reduce(stats)                       # SUM
+    return stats
+
+
 def two_group_adam(params, lr, weight_decay, never_used=(), second=(), second_lr=None, second_weight_decay=0.0, betas=(0.9, 0.999),
                    precision="fp16"):
     """FlatAdam in the layout of the reference's optimizer: always the two groups [other, RRDB] (LLFlow_model.py:110-118,
@@ -512,7 +529,7 @@ class Stage1Trainer(Trainer):
 
     def __init__(self, net, lr_G=1e-4, weight_decay_G=0.0, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0,
                  device_state=False, precision="fp16", discriminator=None, disc_start=10000, disc_weight=0.8, disc_factor=1.0,
-                 codebook_usage=False, codebook_restart=0, restart_threshold=0):
+                 codebook_usage=False, codebook_restart=0, restart_threshold=0, codebook_ema=None, ema_eps=1e-5):
         """lr_G: a starting point, not a tuned value (the reference sets `self.learning_rate` from a config it does not ship).
         discriminator: an NLayerDiscriminator on the net's device, or None (no GAN term: the step and every file are what they were);
         disc_start / disc_weight / disc_factor: taming's defaults for the VQGAN configs.
@@ -531,8 +548,22 @@ class Stage1Trainer(Trainer):
         restarts all the same.  Adam's step count is ONE device scalar shared by every parameter: a re-seeded row starts again from zero
         moments but under the run's global bias correction (1 - beta^t, t the run's step count), not a fresh t = 1 -- late in a
         run its first update is about (1 - beta1) / sqrt(1 - beta2) lr (1.58 lr at this stage's betas) where a new parameter's is lr.  The window is state: it travels in the `.state` file with P
-        and the threshold, and a resume under other values is refused.  World size > 1: exchange_restart_inputs."""
+        and the threshold, and a resume under other values is refused.  World size > 1: exchange_restart_inputs.
+        codebook_ema: a decay d in (0, 1) moves the codebook by the reference's EmbeddingEMA rule instead of a gradient (quantize.py:345-358,
+        426-437; csrc/vq_ema.hip); None (the default) is off: nothing new is launched, and the step and every file are what they were, bit
+        for bit.  On: the embedding stops requiring a gradient and is declared `never_used` -- Adam keeps its moments at zero, applies no
+        update and no weight decay -- the codebook term becomes beta mean((z_q.detach() - z)^2) alone (dE is not computed), and
+        `cluster_size` (fp32 [K], zeros) and `embed_avg` (fp32 [K, 3], the codebook's clone, :336-339) become trainer state.  After
+        `opt.step()` of every step, skipped by the GradScaler or not (no gradient is involved): stats of this step's indices and latents
+        (ops.vq_ema_stats), exchange_ema_stats, ops.vq_ema_update with (d, ema_eps) -- the reference's arithmetic: the step's lookup used the
+        old rows, the backward never reads the codebook.  A code nothing selects only decays: from cluster_size = 0 its smoothed size is
+        about eps and its row embed_avg / ~eps, far from every latent, and it stays dead.  So use it with codebook_restart: on the restart
+        steps, AFTER that step's EMA update, ops.vq_restart_ema re-seeds codebook and embed_avg rows alike and sets their cluster_size to
+        1.0.  Both tensors travel in the `.state` file with d and eps; a resume under other values, or with the key and the option not
+        both present, is refused.  <iter>_VQ.pth keeps VQModel's keys."""
         self.codebook_usage = bool(codebook_usage)
+        self.codebook_ema, self.ema_eps = (None if codebook_ema is None else float(codebook_ema)), float(ema_eps)
+        assert self.codebook_ema is None or (0.0 < self.codebook_ema < 1.0 and self.ema_eps >= 0.0), (codebook_ema, ema_eps)
         self.codebook_restart, self.restart_threshold = int(codebook_restart), int(restart_threshold)
         assert self.codebook_restart >= 0 and self.restart_threshold >= 0, (codebook_restart, restart_threshold)
         self.restart_window = None                   # off: ops.vq_usage is handed no total, as ever
@@ -541,15 +572,24 @@ class Stage1Trainer(Trainer):
             p.requires_grad_(True)
         named = list(net.named_parameters())
         never = [p for n, p in named if n.startswith(STAGE1_NEVER_USED)]
+        E = net.quantize.embedding.weight
+        if self.codebook_ema is not None:            # in the flat layout as ever (one `.state` layout), outside what Adam updates
+            never.append(E)
         super().__init__(net.train(), [p for n, p in named if not n.startswith(STAGE1_NEVER_USED)], precision, [p for _, p in named], lr_G,
                          weight_decay_G, never_used=never, betas=(0.5, 0.9))
         self.net = self.netG                         # `netG`: the name the driver and the checkpoint code read
         self.discriminator, self.opt_d = discriminator, None
         self.disc_start, self.disc_weight, self.disc_factor = int(disc_start), float(disc_weight), float(disc_factor)
         self.global_step = 0                         # Lightning's global_step: steps taken so far (on_resume restores it)
+        self.cluster_size = self.embed_avg = None
+        if self.codebook_ema is not None:
+            E.requires_grad_(False)                  # autograd.VQStraightThroughFn then computes no dE
+            net.quantize.ema_update = True           # VectorQuantizer2.loss_weights(): (beta, 0)
+            self.cluster_size = torch.zeros(E.shape[0], dtype=torch.float32, device=E.device)
+            self.embed_avg = E.detach().clone()
         if self.codebook_restart:
             # the parameters are views of FlatGroup.w: the embedding's rows of w, exp_avg and exp_avg_sq sit at one static offset
-            E, g0, off = net.quantize.embedding.weight, self.opt.groups[0], 0
+            g0, off = self.opt.groups[0], 0
             for p in g0.params:
                 if p is E:
                     break
@@ -573,13 +613,17 @@ class Stage1Trainer(Trainer):
         return {} if self.discriminator is None else {"D": self.discriminator}
 
     def extra_state(self):
-        """D's Adam and GradScaler state, and the restart's window with its two settings, travel as further keys of the `.state` file."""
+        """D's Adam and GradScaler state, the restart's window with its two settings, and the EMA's two tensors with theirs, travel as
+        further keys of the `.state` file."""
         extra = {}
         if self.discriminator is not None:
             extra[DISC_KEY] = {"optimizer": checkpoint.adam_state_dict(self.opt_d), "scaler": self.opt_d.scaler_state_dict()}
         if self.codebook_restart:
             extra[RESTART_KEY] = {"window": self.restart_window.cpu().clone(), "every": self.codebook_restart,
                                   "threshold": self.restart_threshold}
+        if self.codebook_ema is not None:
+            extra[EMA_KEY] = {"cluster_size": self.cluster_size.cpu().clone(), "embed_avg": self.embed_avg.cpu().clone(),
+                              "decay": self.codebook_ema, "eps": self.ema_eps}
         return extra
 
     def load_extra_state(self, state):
@@ -599,6 +643,19 @@ class Stage1Trainer(Trainer):
         else:
             assert saved is None, ("the .state file carries a restart window (it was written with --codebook-restart %d) and this run has "
                                    "no --codebook-restart: name it again" % saved["every"])
+        saved = state.get(EMA_KEY)
+        if self.codebook_ema is not None:
+            assert saved is not None, ("--codebook-ema: the .state file carries no cluster_size / embed_avg (it was written without "
+                                       "--codebook-ema, by a run whose codebook followed its gradient)")
+            assert (float(saved["decay"]), float(saved["eps"])) == (self.codebook_ema, self.ema_eps), (
+                "--codebook-ema: the .state file was written with --codebook-ema %r --ema-eps %r and this run has %r and %r: the averages "
+                "would go on under another rule partway through; name the same values again"
+                % (saved["decay"], saved["eps"], self.codebook_ema, self.ema_eps))
+            self.cluster_size.copy_(saved["cluster_size"])
+            self.embed_avg.copy_(saved["embed_avg"])
+        else:
+            assert saved is None, ("the .state file carries an EMA codebook's state (it was written with --codebook-ema %r --ema-eps %r) and "
+                                   "this run has no --codebook-ema: name both again" % (saved["decay"], saved["eps"]))
 
     def on_resume(self, step):
         self.global_step = step                      # what `disc_start` and the restart's period are compared with
@@ -615,8 +672,12 @@ class Stage1Trainer(Trainer):
         return {"codebook_active": active[0], "codebook_perplexity": perplexity[0]}
 
     def _codebook_terms(self, idx):
-        """What follows `opt.step()` for the codebook's bookkeeping: the usage terms, the restart's window and, on its steps, the restart
-        itself.  Both options off: nothing is launched and {} comes back."""
+        """What follows `opt.step()` for the codebook's bookkeeping: the EMA update, the usage terms, the restart's window and, on its
+        steps, the restart itself (after that step's EMA update).  Every option off: nothing is launched and {} comes back."""
+        if self.codebook_ema is not None:
+            E = self.net.quantize.embedding.weight.data
+            stats = exchange_ema_stats(ops.vq_ema_stats(idx, self.net.last_latent, E.shape[0]), idx.numel())
+            ops.vq_ema_update(stats, self.cluster_size, self.embed_avg, E, self.codebook_ema, self.ema_eps)
         terms = self._usage_terms(idx) if self.codebook_usage else {}
         if not self.codebook_restart:
             return terms
@@ -627,7 +688,11 @@ class Stage1Trainer(Trainer):
             w, m, v = self._restart_rows
             window, z = exchange_restart_inputs(self.restart_window, self.net.last_latent)
             offset = (self.global_step // self.codebook_restart) * RESTART_OFFSET_STEP
-            _, terms["codebook_restarted"] = ops.vq_restart(window, z, w, offset, self.restart_threshold, m, v)
+            if self.codebook_ema is not None:
+                _, terms["codebook_restarted"] = ops.vq_restart_ema(window, z, w, self.embed_avg, self.cluster_size, offset,
+                                                                    self.restart_threshold, EMA_SEED_SIZE)
+            else:
+                _, terms["codebook_restarted"] = ops.vq_restart(window, z, w, offset, self.restart_threshold, m, v)
         return terms
 
     def invalidate(self):

@@ -130,6 +130,43 @@ int glare_vq_restart_f32(long long* window_counts, long long threshold, const fl
                          long long offset, float* codebook, float* exp_avg, float* exp_avg_sq, long long* n_dead, long long* n_restarted,
                          void* workspace, size_t workspace_bytes, glare_stream_t stream);
 
+/* The restart under an EMA codebook (below): the same dead codes, ranking, header, source tokens t_j and counts as glare_vq_restart_f32,
+ * with the same workspace.  For a written row: codebook[d_j] = embed_avg[d_j] = z_tokens[t_j] (bit copies) and cluster_size[d_j] =
+ * seed_size -- the code restarts as the mean of seed_size tokens at its new place; every other element of the three tensors keeps its bits.
+ * No Adam moments: under EMA the codebook is no Adam parameter.  embed_avg [n_codes][3], cluster_size [n_codes] fp32, in place.
+ * GLARE_ERR_INVALID also for a null embed_avg / cluster_size and a seed_size that is negative or not finite; the rest as above. */
+int glare_vq_restart_ema_f32(long long* window_counts, long long threshold, const float* z_tokens, long long n_tokens, int n_codes, int dim,
+                             long long offset, float seed_size, float* codebook, float* embed_avg, float* cluster_size, long long* n_dead,
+                             long long* n_restarted, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+
+/* ---- a5, EMA form: the codebook as the moving average of the latents that select each code (csrc/vq_ema.hip) ----------------
+ * Replaces EmbeddingEMA.cluster_size_ema_update / embed_avg_ema_update / weight_update and the one-hot statistics
+ * EMAVectorQuantizer.forward hands them (code/models/modules/quantize.py:345-358, 426-434).  State beside the codebook E [n_codes][3]:
+ * cluster_size [n_codes] (zeros at first) and embed_avg [n_codes][3] (E at first, :336-339), all fp32.  Per training step, idx / z the
+ * indices glare_vq_nearest_f32 wrote and the latents it read:
+ * glare_vq_ema_stats_f32:   stats[k] = {s_k0, s_k1, s_k2, n_k},  n_k = #{i : idx[i] = k},  s_k = sum_{i : idx[i] = k} z[i]    (:428, :431)
+ *   idx_i64 [n_tokens] int64, z_tokens [n_tokens][3] fp32 -> stats [n_codes][4] fp32, every element written.  A fixed-order per-code sum
+ *   as glare_vq_backward_f32's dE: the token axis in <= 32 segments, a code's tokens added in token order within a segment, the
+ *   segments' partial sums in segment order; the count is an integer until its last store and exact.  No address depends on an index:
+ *   an index outside [0, n_codes) selects nothing (DEVIATION from one_hot, which raises).
+ * glare_vq_ema_update_f32:  d = decay, all three tensors in place                                                   (:346, :349, :352-358)
+ *   cluster_size[k] = d cluster_size[k] + (1 - d) n_k;   embed_avg[k] = d embed_avg[k] + (1 - d) s_k
+ *   n = sum_k cluster_size[k];   smoothed_k = (cluster_size[k] + eps) / (n + n_codes eps) * n;   codebook[k] = embed_avg[k] / smoothed_k
+ *   DEVIATION: n == 0 exactly (no token ever counted) leaves the codebook as it was, where the reference writes 0 / 0; the two state
+ *   tensors are decayed all the same.  1 - d is formed in fp32 (exact for d >= 0.5); n is summed in fp64 in a fixed two-level order
+ *   and rounded to fp32 once; everything else is one fp32 rounding per operation, in the order written above.  Three launches.
+ *   A separate call so that stats can be summed over ranks in between.  A code nothing selects only decays: from cluster_size 0 its
+ *   smoothed size is about eps and its row embed_avg / ~eps -- far away; use with glare_vq_restart_ema_f32.
+ * Both: no atomics of any kind, the same bits on every run.  workspace: glare_vq_ema_workspace_bytes(n_tokens, n_codes) bytes serve either
+ * call (0: not a size the kernels take), 8-byte aligned.  GLARE_ERR_INVALID: a null pointer, a non-positive size, a workspace that is not
+ * 8-byte aligned, decay outside (0, 1), eps < 0 (or either a NaN); GLARE_ERR_UNSUPPORTED: dim != 3, n_tokens > 2^24 (the float count must
+ * stay exact), n_codes > GLARE_VQ_USAGE_MAX_CODES; GLARE_ERR_WORKSPACE as elsewhere -- all before any launch. */
+size_t glare_vq_ema_workspace_bytes(long long n_tokens, int n_codes);
+int glare_vq_ema_stats_f32(const long long* idx_i64, const float* z_tokens, long long n_tokens, int n_codes, int dim, float* stats,
+                           void* workspace, size_t workspace_bytes, glare_stream_t stream);
+int glare_vq_ema_update_f32(const float* stats, int n_codes, int dim, float decay, float eps, float* cluster_size, float* embed_avg,
+                            float* codebook, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+
 /* ---- a1/a6/a8: im2col-free direct convolution on bf16 MFMA ----------------------------------
  * Replaces torch.nn.Conv2d / F.conv2d for the 3x3 and 1x1 convolutions of the VQGAN
  * encoder/decoder, AttnBlock projections, WarpBlock.offset, DCNv2Pack.conv_offset and the flow
