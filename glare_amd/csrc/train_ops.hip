@@ -687,6 +687,9 @@ extern "C" int glare_im2col_t_bf16(const void* x_nhwc, int B, int H, int W, int 
   const int IH = upsample ? 2 * H : H, IW = upsample ? 2 * W : W;
   p.OH = stride == 1 ? IH + 2 * pad - ksize + 1 : (IH + 1 - ksize) / 2 + 1;   // stride 2: (0,1,0,1) padding
   p.OW = stride == 1 ? IW + 2 * pad - ksize + 1 : (IW + 1 - ksize) / 2 + 1;
+  // an image the filter does not fit into has no output pixel: a 1-pixel side under the stride-2 3x3 gives IH + 1 - ksize = -1, which
+  // the division above truncates to OH = 1 (a pixel the conv does not have)
+  if (IH + (stride == 2 ? 1 : 2 * pad) < ksize || IW + (stride == 2 ? 1 : 2 * pad) < ksize) return GLARE_ERR_INVALID;
   p.P = (long long)B * p.OH * p.OW;
   if (ldp < p.P) return GLARE_ERR_INVALID;
   p.x = static_cast<const a16_t*>(x_nhwc); p.col = static_cast<a16_t*>(colT); p.ldp = ldp;

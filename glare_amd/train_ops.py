@@ -118,6 +118,8 @@ def pool2_sum(g):
     require_cuda(g)
     assert g.dtype == act_dtype() and g.is_contiguous()
     B, H2, W2, C = g.shape
+    # the kernel indexes g as [B][2H][2W]: with an odd side floored away, every image after the first would be read at the wrong place
+    assert H2 % 2 == 0 and W2 % 2 == 0, "pool2_sum sums whole 2x2 blocks: %dx%d has an odd side" % (H2, W2)
     out = torch.empty(B, H2 // 2, W2 // 2, C, dtype=act_dtype(), device=g.device)
     check(_lib.lib().glare_pool2_sum_bf16(ptr(g), ptr(out), B, H2 // 2, W2 // 2, C, stream_handle()),
           "glare_pool2_sum_bf16")

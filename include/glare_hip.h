@@ -666,6 +666,7 @@ int glare_reduce_parts_grouped_f32(const float* parts, int n_groups, int n_parts
  * glare_im2col_t_bf16: colT[row_base + c*k*k + tap][p] = x[b, oy*stride+ty-pad, ox*stride+tx-pad, c] (0 outside), p the
  *   flattened output pixel (b, oy, ox); x bf16 NHWC [B][H][W][pitch], channels [off, off+Ci), optionally seen through
  *   the nearest x2 upsample; stride 2 uses Downsample's (0,1,0,1) padding (encoder_decoder.py:71-74, pass pad = 0).
+ *   An image the padded filter does not fit into (a 1-pixel side under the stride-2 3x3) has no output pixel: invalid.
  *   Columns [P, ldp) are zero-filled (ldp % 64 == 0); ones_row >= 0 additionally writes a row of ones (p < P), which
  *   turns the weight-gradient GEMM's extra column into the bias gradient.  The weight gradient of a k x k conv is then
  *   dW[co][ci*k*k + tap] = gemm_nt(gO^T [Co][P], colT) -- the layout of an OIHW filter (cuDNN wgrad in the reference).
