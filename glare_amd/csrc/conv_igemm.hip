@@ -351,7 +351,10 @@ extern "C" int glare_conv2d_bf16(const glare_conv_desc* d, glare_stream_t stream
   if (d->in2 && ((d->Cin2 % 8) || (d->in2_pitch % 8) || (d->in2_off % 8) || d->Cin2 <= 0)) return GLARE_ERR_UNSUPPORTED;
   if (d->out_mode < GLARE_OUT_NHWC_BF16 || d->out_mode > GLARE_OUT_PLANAR_BF16) return GLARE_ERR_INVALID;
   if (d->residual && d->out_mode > GLARE_OUT_NHWC_F32) return GLARE_ERR_UNSUPPORTED;
-  if (d->in_off + d->Cin > d->in_pitch || d->out_off + d->Cout > d->out_pitch) return GLARE_ERR_INVALID;
+  if (d->in_off < 0 || d->out_off < 0 || d->in_off + d->Cin > d->in_pitch || d->out_off + d->Cout > d->out_pitch) return GLARE_ERR_INVALID;
+  if (d->in2 && (d->in2_off < 0 || d->in2_off + d->Cin2 > d->in2_pitch)) return GLARE_ERR_INVALID;
+  // the residual's channel window lies inside its records, like the other operands' (glare_conv1x1_ws_bf16 checks the same)
+  if (d->residual && (d->res_off < 0 || d->res_off + d->Cout > d->res_pitch)) return GLARE_ERR_INVALID;
 
   ConvParams p;
   p.in0 = (const a16_t*)d->in;

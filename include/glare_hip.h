@@ -197,7 +197,7 @@ typedef struct glare_conv_desc {
   int Cin, in_pitch, in_off;
   int Cin2, in2_pitch, in2_off;
   int Cout, out_pitch, out_off; /* planar modes: out_pitch = number of planes per image            */
-  int res_pitch, res_off;
+  int res_pitch, res_off;    /* every channel window lies inside its record: 0 <= off, off + C <= pitch (GLARE_ERR_INVALID) */
   int ksize;                 /* 1 or 3                                                             */
   int stride;                /* 1 (pad ksize/2) or 2 (3x3 only, pad (0,1,0,1))                     */
   int upsample;              /* 0: none; 1: nearest x2 on the input first (Upsample, encoder_decoder.py:43-52);   */
