@@ -710,3 +710,33 @@ class ImageAffineFn(torch.autograd.Function):
 
 def image_affine(x, mul, add):
     return ImageAffineFn.apply(x, mul, add)
+
+
+@_lib.keeps_precision
+class VQSemanticFn(torch.autograd.Function):
+    """The semantic guidance term (VQModel_arch.py:85-88): F.mse_loss(relu(conv1x1(quant; weight, bias)), feat) as ONE fused kernel
+    (ops.vq_semantic, csrc/vq_semantic.hip) that also leaves the three unit gradients, which is all the tape keeps -- the [N, 256]
+    activation never exists.  quant fp32 NHWC [.., 3], weight fp32 [256, 3, 1, 1], bias fp32 [256], feat 16-bit NHWC [.., 256] (constant:
+    no gradient).  Backward: one launch that multiplies the unit gradients by the upstream device scalar (the term's weights and, under
+    fp16, the loss scale); inside data_grad_only() only quant's."""
+
+    @staticmethod
+    def forward(ctx, quant, weight, bias, feat):
+        loss, dq, dw, db = ops.vq_semantic(quant.float(), weight.detach().float(), bias.detach().float(), feat.detach())
+        ctx.shapes = (tuple(quant.shape), tuple(weight.shape))
+        ctx.save_for_backward(dq, dw, db)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, dw, db = ctx.saved_tensors
+        params = not _DATA_GRAD_ONLY and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        gq, gw, gb = ops.vq_semantic_scale(g.detach().float().reshape(1).contiguous(), dq, dw if params else None, db if params else None)
+        qshape, wshape = ctx.shapes
+        return (gq.view(qshape) if ctx.needs_input_grad[0] else None, gw.view(wshape) if params and ctx.needs_input_grad[1] else None,
+                gb if params and ctx.needs_input_grad[2] else None, None)
+
+
+def vq_semantic(quant_nhwc, weight, bias, feat_nhwc):
+    """-> the scalar mse of conv_semantic(quant) against the feature map."""
+    return VQSemanticFn.apply(quant_nhwc, weight, bias, feat_nhwc)

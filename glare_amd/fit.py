@@ -10,6 +10,7 @@ code/train_stage3.py:138-300 over models/base_model.py:46-83 and models/lr_sched
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-usage        (log the codebook's use; glare_amd.evaluate stage1 scores the run)
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-restart 100  (every 100 steps, re-seed the codes nothing selected)
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-ema 0.99 --codebook-restart 100   (an EMA codebook, no gradient)
+    python -m glare_amd.fit stage1 --root LOLdataset --out prior --vgg19 vgg19-dcbb9e9d.pth [--semantic-weight 0.1]   (semantic guidance)
 
 Stage 1 trains the VQGAN prior itself (VQModel_arch.py:98-101, 148-157) on the ground-truth half of the pairs and writes
 <out>/models/<iter>_VQ.pth under the reference's VQModel key names: what `--net-vq` of stages 2 and 3, `evaluate` and `enhance` load.
@@ -17,6 +18,8 @@ Stage 1 trains the VQGAN prior itself (VQModel_arch.py:98-101, 148-157) on the g
 files; stage 3: the VGG16-feature loss, --vgg16 alone; losses.load_vgg16 refuses a file that lacks a tensor).  The loss networks are frozen and
 are written to no checkpoint: a resumed run names the same files again (the .state records that the run had the term, and a resume
 without it, or with another --perceptual-weight, is refused).
+--vgg19 adds stage 1's semantic guidance term (VQModel_arch.py:85-88: the codes through conv_semantic against VGG19 relu3_4 of the input)
+from the user's VGG19 file (losses.load_vgg19, strict); the same rules hold for it: frozen, in no checkpoint, named again on a resume.
 The reference ships no stage-1 configuration (its prior is a download): `lr_G` 1e-4 is a starting point, not a tuned value.
 
 What is mirrored: the option keys and their per-stage values, the seeding, the index order of the reference's DataLoader, the
@@ -306,6 +309,14 @@ def check_perceptual_options(stage, vgg16=None, lpips_heads=None, perceptual_wei
         raise ValueError("--perceptual-weight needs --vgg16 and --lpips-heads: without them stage1 has no perceptual term to weigh")
 
 
+def check_semantic_options(stage, vgg19=None, semantic_weight=None):
+    """The refusals of --vgg19 / --semantic-weight: ValueError with the reason, before anything is built."""
+    if stage != "stage1" and (vgg19 or semantic_weight is not None):
+        raise ValueError(SEMANTIC_REFUSAL)
+    if semantic_weight is not None and not vgg19:
+        raise ValueError("--semantic-weight needs --vgg19: without the VGG19 file stage1 has no semantic term to weigh")
+
+
 def check_restart_options(stage, codebook_restart=0, restart_threshold=None):
     """The refusals of --codebook-restart / --restart-threshold: ValueError with the reason, before anything is built."""
     if stage != "stage1" and (codebook_restart or restart_threshold is not None):
@@ -342,18 +353,32 @@ def build_perceptual(stage, device, vgg16=None, lpips_heads=None):
     return net.to(device).eval()
 
 
+def build_semantic(device, vgg19=None):
+    """Stage 1's frozen VGG19 relu3_4 extractor from the user's file (losses.load_vgg19, strict; `.loaded_keys`: what it loaded), or None
+    without --vgg19."""
+    from . import losses
+
+    if not vgg19:
+        return None
+    net = losses.SemanticTarget()
+    net.loaded_keys = losses.load_vgg19(net, vgg19)
+    return net.to(device).eval()
+
+
 def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16", gan=False, net_d=None, vgg16=None,
                   lpips_heads=None, perceptual_weight=None, codebook_usage=False, codebook_restart=0, restart_threshold=None,
-                  codebook_ema=None, ema_eps=None):
+                  codebook_ema=None, ema_eps=None, vgg19=None, semantic_weight=None):
     """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer.  gan (stage 1 only): with the
     patch discriminator (taming's initialisation under the run's seed, or the `_D.pth` file net_d).  vgg16 / lpips_heads: the weight
     files of the perceptual term (stage 1: LPIPS, both files; stage 3: the VGG16-feature loss, the backbone alone); perceptual_weight:
     stage 1's factor on it (default 1.0).  The loss network is frozen and is written to no checkpoint: a resumed run names the files again.
     codebook_usage, codebook_restart / restart_threshold, codebook_ema / ema_eps (stage 1 only): Stage1Trainer's; off, the trainer is built
-    without the keywords."""
+    without the keywords.  vgg19 / semantic_weight (stage 1 only): the VGG19 file of the semantic guidance term and its factor (default 0.1);
+    frozen and in no checkpoint like the perceptual network."""
     from . import modules as M
 
     check_perceptual_options(stage, vgg16, lpips_heads, perceptual_weight)
+    check_semantic_options(stage, vgg19, semantic_weight)
     tr = options["train"]
     perceptual = build_perceptual(stage, device, vgg16, lpips_heads)       # None without the options: the trainers' own default
     if stage == "stage1" and graph:
@@ -382,7 +407,9 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
                                    **({"codebook_restart": int(codebook_restart), "restart_threshold": int(restart_threshold or 0)}
                                       if codebook_restart else {}),
                                    **({"codebook_ema": float(codebook_ema), "ema_eps": 1e-5 if ema_eps is None else float(ema_eps)}
-                                      if codebook_ema is not None else {}))
+                                      if codebook_ema is not None else {}),
+                                   **({"semantic": build_semantic(device, vgg19),
+                                       "semantic_weight": 0.1 if semantic_weight is None else float(semantic_weight)} if vgg19 else {}))
     if stage == "stage2":
         return train.Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
                                    train_rrdb=bool(options["network_G"].get("train_RRDB", False)), precision=precision)
@@ -396,13 +423,16 @@ CODEBOOK_RESTART_REFUSAL = ("--codebook-restart / --restart-threshold are stage1
                             "and 3 read a frozen one, which has no dead codes to revive)")
 CODEBOOK_EMA_REFUSAL = ("--codebook-ema / --ema-eps are stage1 options: stage1 is the stage that trains the codebook (stages 2 and 3 read a "
                         "frozen one, which nothing updates)")
+SEMANTIC_REFUSAL = ("--vgg19 / --semantic-weight are stage1 options: the semantic guidance term belongs to the VQGAN prior's codebook loss "
+                    "(VQModel_arch.py:85-88); stages 2 and 3 read a frozen prior")
 GAN_REFUSAL = "--gan is a stage1 option: the patch discriminator belongs to the VQGAN prior's objective (stages 2 and 3 train no GAN term)"
 LPIPS_REFUSAL = ("stage1's perceptual term is LPIPS and needs both files: --vgg16 (the VGG16 backbone) and --lpips-heads (the five linear "
                  "heads, taming's / the lpips package's vgg.pth); one without the other would leave half the network at its initialisation")
 PERCEPTUAL_STAGE3_REFUSAL = ("--lpips-heads / --perceptual-weight are stage1 options: stage3's perceptual term is the VGG16-feature MSE with its "
                              "fixed factor 0.01 (VQLLFLOWD_model.py:217-223) and takes --vgg16 alone")
 PERCEPTUAL_RESUME_REFUSAL = ("the .state file was written by a run with %s and this one has %s: the objective would change partway through "
-                             "the run; name the same --vgg16 / --lpips-heads / --perceptual-weight again (the loss network is in no checkpoint)")
+                             "the run; name the same --vgg16 / --lpips-heads / --perceptual-weight / --vgg19 / --semantic-weight again (the loss networks are in "
+                             "no checkpoint)")
 PERCEPTUAL_STAGE2_REFUSAL = "--vgg16 / --lpips-heads / --perceptual-weight are stage1 / stage3 options: stage2's objective is the flow's NLL alone"
 GRAPH_REFUSAL = "--graph is not available for stage1: its step is not captured into a hipGraph (GraphedStep covers stages 2 and 3)"
 
@@ -508,6 +538,9 @@ def parse_args(argv=None):
                                                   "stage1 with --lpips-heads: the LPIPS term; stage3: the VGG16-feature perceptual term")
     ap.add_argument("--lpips-heads", default=None, help="stage1: the LPIPS linear heads (taming's / the lpips package's vgg.pth)")
     ap.add_argument("--perceptual-weight", type=float, default=None, help="stage1: factor on the LPIPS term (default 1.0)")
+    ap.add_argument("--vgg19", default=None, help="stage1: VGG19 weights (torchvision's vgg19 state dict, vgg19-dcbb9e9d.pth; also the key form "
+                                                  "vgg_net.convX_Y): adds the semantic guidance term on the codebook (relu3_4)")
+    ap.add_argument("--semantic-weight", type=float, default=None, help="--vgg19: factor on the semantic term inside the codebook loss (default 0.1)")
     ap.add_argument("--codebook-usage", action="store_true", help="stage1: log codebook_active / codebook_perplexity of every step's indices, and "
                                                                    "the test split's codebook use with the closing validation")
     ap.add_argument("--codebook-restart", type=int, default=0, metavar="P",
@@ -532,6 +565,7 @@ def parse_args(argv=None):
         check_restart_options(args.stage, args.codebook_restart, args.restart_threshold)
         check_ema_options(args.stage, args.codebook_ema, args.ema_eps)
         check_perceptual_options(args.stage, args.vgg16, args.lpips_heads, args.perceptual_weight)
+        check_semantic_options(args.stage, args.vgg19, args.semantic_weight)
     except ValueError as e:
         ap.error(str(e))
 
@@ -570,10 +604,13 @@ def main(argv=None):
     trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision, gan=args.gan, net_d=net_d,
                             vgg16=args.vgg16, lpips_heads=args.lpips_heads, perceptual_weight=args.perceptual_weight,
                             codebook_usage=args.codebook_usage, codebook_restart=args.codebook_restart, restart_threshold=args.restart_threshold,
-                            codebook_ema=args.codebook_ema, ema_eps=args.ema_eps)
+                            codebook_ema=args.codebook_ema, ema_eps=args.ema_eps, vgg19=args.vgg19, semantic_weight=args.semantic_weight)
     if args.vgg16:        # the opening line of a run with a perceptual term: which files it was built from
         print(json.dumps({"perceptual": type(trainer.perceptual).__name__, "vgg16": args.vgg16, "lpips_heads": args.lpips_heads,
                           "tensors_loaded": len(trainer.perceptual.loaded_keys)}), flush=True)
+    if args.vgg19:        # ... and of a run with the semantic term
+        print(json.dumps({"semantic": type(trainer.semantic).__name__, "vgg19": args.vgg19, "semantic_weight": trainer.semantic_weight,
+                          "tensors_loaded": len(trainer.semantic.loaded_keys)}), flush=True)
     step_fn, batch_fn = graphed_fns(trainer, dataset) if args.graph else (None, None)
     validate_fn = None
     # stage 3 scores the inference path, stage 1 the prior's own reconstruction of the ground truth; stage 2 has nothing to score

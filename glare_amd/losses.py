@@ -195,6 +195,70 @@ class LPIPSLoss(HipModule):
         return total.mean()
 
 
+VGG19_RELU3_4 = (64, 64, "M", 128, 128, "M", 256, 256, 256, 256)      # torchvision cfg 'E' down to relu3_4: convs 0 2 5 7 10 12 14 16, pools 4 9
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)   # vgg_arch.py:134-137, for an image in [0, 1]
+
+
+class SemanticTarget(HipModule):
+    """The target of stage 1's semantic guidance term: VGG19 down to relu3_4 on the input image, as the reference's
+    VGGFeatureExtractor(['relu3_4']) that VQModel builds (VQModel_arch.py:56-61) computes it with use_input_norm=True: (x - mean) / std with
+    ImageNet's statistics on a [0, 1] image (vgg_arch.py:134-152), then `features[:18]` of torchvision's vgg19 -- two 2x2 pools, so the map is
+    H/4 x W/4 with 256 channels: the f4 latent's size.  `features.<torchvision index>.weight|bias` are the parameter names, so
+    vgg19-dcbb9e9d.pth loads unchanged (load_vgg19).  The trunk runs on the taped HIP convs used as plain forwards; every parameter is
+    frozen and the module stays in eval mode; the filters are packed once per precision (ops.FrozenPacks)."""
+
+    def __init__(self):
+        super().__init__()
+        layers, cin = [], 3
+        for v in VGG19_RELU3_4:
+            if v == "M":
+                layers.append(nn.MaxPool2d(kernel_size=2, stride=2))
+            else:
+                layers += [nn.Conv2d(cin, v, 3, padding=1), nn.ReLU(inplace=True)]
+                cin = v
+        self.features = nn.Sequential(*layers)
+        self.register_buffer("mean", torch.tensor(IMAGENET_MEAN)[None, :, None, None])
+        self.register_buffer("std", torch.tensor(IMAGENET_STD)[None, :, None, None])
+        for p in self.parameters():
+            p.requires_grad = False
+        super().train(False)
+
+    def train(self, mode=True):
+        return super().train(False)       # a frozen loss network: eval mode whatever the caller's .train() says
+
+    def _frozen_packs(self):
+        cache = self.__dict__.setdefault("_hip_cache", {})
+        if "frozen" not in cache:
+            cache["frozen"] = ops.FrozenPacks(list(self.features.parameters()))
+        return cache["frozen"]
+
+    def _affine(self):
+        def build():      # (x - mean) / std as x * mul + add, the two vectors formed in fp64
+            mean, std = self.mean.detach().double().reshape(-1), self.std.detach().double().reshape(-1)
+            return (1.0 / std).float().contiguous(), (-mean / std).float().contiguous()
+        return self._packed("affine", build)
+
+    def forward(self, img):
+        """img: NHWC fp32 in [0, 1], H and W multiples of 4 -> relu3_4 as 16-bit NHWC [B, H/4, W/4, 256], no tape."""
+        B, H, W, C = img.shape
+        if C != 3 or H % 4 or W % 4:
+            raise ValueError("SemanticTarget: an NHWC 3-channel image with H and W multiples of 4 is asked (two 2x2 pools down to the "
+                             "latent's size); got %s" % (tuple(img.shape),))
+        self._frozen_packs()
+        with torch.no_grad():
+            mul, add = self._affine()
+            h = A.image_affine(img.float().contiguous(), mul, add)
+            for m in self.features:
+                if isinstance(m, nn.Conv2d):                              # conv + the ReLU that follows it, fused
+                    if m.in_channels == 3:
+                        h = A.conv2d_small(h, m.weight, m.bias, layout="nhwc", act="relu")
+                    else:
+                        h = A.conv2d(h, m.weight, m.bias, act="relu")
+                elif isinstance(m, nn.MaxPool2d):
+                    h = A.maxpool2(h)
+        return h
+
+
 _BACKBONE_KEY = re.compile(r"^(?:features|vgg_model|net\.slice[1-5])\.(\d+)\.(weight|bias)$")
 
 
@@ -247,4 +311,53 @@ def load_vgg16(module, vgg16_file, heads_file=None):
             p.copy_(v.to(p.dtype))
     if hasattr(module, "invalidate"):
         module.invalidate()
+    return [name for name, _, _ in plan]
+
+
+def _vgg19_conv_names():
+    """{'convB_I': torchvision index} of vgg19.features, the names the reference's extractor gives its layers (vgg_arch.py NAMES['vgg19'])."""
+    names, idx, block, conv = {}, 0, 1, 1
+    for v in (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"):     # cfg 'E'
+        if v == "M":
+            idx, block, conv = idx + 1, block + 1, 1
+        else:
+            names["conv%d_%d" % (block, conv)] = idx
+            idx, conv = idx + 2, conv + 1
+    return names
+
+
+_VGG_NET_KEY = re.compile(r"^vgg_net\.(conv\d_\d)\.(weight|bias)$")
+_FEATURES_KEY = re.compile(r"^features\.(\d+)\.(weight|bias)$")
+
+
+def load_vgg19(module, vgg19_file):
+    """The strict loader of a SemanticTarget, in the manner of load_vgg16: fills it from a file (a path, or a state dict) under torchvision's
+    keys (`features.N.weight|bias`, what vgg19-dcbb9e9d.pth holds) or the reference extractor's (`vgg_net.conv3_4.weight`, ...).  The
+    classifier and the deeper convs are ignored.  Every tensor of the trunk must be found with its shape, else ValueError names the
+    missing / mismatched keys (a VGG16 file has no conv at `features.16`: its index 16 is a pool).  Returns the list of the keys loaded."""
+    if vgg19_file is None:
+        raise ValueError("load_vgg19: the VGG19 file is required")
+    by_name, src = _vgg19_conv_names(), {}
+    for key, v in _state_dict_of(vgg19_file).items():
+        m, n = _FEATURES_KEY.match(key), _VGG_NET_KEY.match(key)
+        if m:
+            src[(int(m.group(1)), m.group(2))] = v
+        elif n and n.group(1) in by_name:
+            src[(by_name[n.group(1)], n.group(2))] = v
+    plan, missing, wrong = [], [], []
+    for name, p in module.named_parameters():
+        m = _FEATURES_KEY.match(name)
+        found = src.get((int(m.group(1)), m.group(2)))
+        if found is None:
+            missing.append(name)
+        elif tuple(found.shape) != tuple(p.shape):
+            wrong.append("%s: %s in the file, %s expected" % (name, tuple(found.shape), tuple(p.shape)))
+        else:
+            plan.append((name, p, found))
+    if missing or wrong:
+        raise ValueError("load_vgg19(%s): missing %s; wrong shape %s" % (type(module).__name__, missing or "none", wrong or "none"))
+    with torch.no_grad():
+        for _, p, v in plan:
+            p.copy_(v.to(p.dtype))
+    module.invalidate()
     return [name for name, _, _ in plan]

@@ -24,7 +24,7 @@ class VQModel(HipModule):
         self.quantize = VectorQuantizer2(n_embed, embed_dim, beta=0.25)
         self.quant_conv = nn.Conv2d(z_channels, embed_dim, 1)
         self.post_quant_conv = nn.Conv2d(embed_dim, z_channels, 1)
-        self.conv_semantic = nn.Sequential(nn.Conv2d(3, 256, 1, 1, 0), nn.ReLU())  # state-dict surface only
+        self.conv_semantic = nn.Sequential(nn.Conv2d(3, 256, 1, 1, 0), nn.ReLU())  # used by train_nhwc(x, vgg_feat) alone
 
     def _conv1x1_latent(self, conv, z):
         B, H, W, C = z.shape
@@ -56,15 +56,31 @@ class VQModel(HipModule):
         self.last_indices = info[2]
         return dec, emb_loss, [to_nchw(f) for f in feats]
 
-    def train_nhwc(self, x_nchw):
+    semantic_weight = 0.1             # VQModel_arch.py:87: emb_loss += 0.1 * semantic_loss
+
+    def train_nhwc(self, x_nchw, vgg_feat=None):
         """The whole autoencoder with a tape (VQModel_arch.py:98-101, forward = decode(encode(x))): x fp32 NCHW image ->
         (xrec fp32 NHWC, qloss scalar, idx int64 [B*h*w]).  The two 1x1 convs of the 3-channel latent run the thin-input conv with
-        weight, bias and data gradients; the codebook layer is autograd.vq_straight_through (csrc/vq_train.hip)."""
+        weight, bias and data gradients; the codebook layer is autograd.vq_straight_through (csrc/vq_train.hip).
+        vgg_feat: None, or the VGG19 relu3_4 map of x (losses.SemanticTarget), 16-bit NHWC [B, h, w, 256] at the latent's size: qloss then
+        carries the semantic guidance term of decode() (:85-88), qloss + semantic_weight * mse(conv_semantic(quant), vgg_feat), as one
+        fused kernel (autograd.vq_semantic), and `last_semantic` holds the detached mse.  `quant` is the straight-through output, so the
+        term's gradient reaches z -- the encoder and quant_conv -- and conv_semantic, never a codebook row (quantize.py:298)."""
         q = self.quantize
+        if vgg_feat is not None:      # refused before anything is launched
+            f = 2 ** (self.encoder.num_resolutions - 1)
+            B, _, H, W = x_nchw.shape
+            if H % f or W % f or tuple(vgg_feat.shape) != (B, H // f, W // f, self.conv_semantic[0].out_channels):
+                raise ValueError("train_nhwc: a %dx%d input (a multiple of %d is asked) has a %dx%d latent and needs vgg_feat [%d, %d, %d, %d]; "
+                                 "got %s" % (H, W, f, H // f, W // f, B, H // f, W // f, self.conv_semantic[0].out_channels, tuple(vgg_feat.shape)))
         h, _ = self.encoder.train_nhwc(x_nchw)
         z = A.conv2d_small(h, self.quant_conv.weight, self.quant_conv.bias, layout="nhwc", out_f32=True)
         w_z, w_e = q.loss_weights()
         zq, qloss, idx = A.vq_straight_through(z, q.embedding.weight, w_z, w_e)
+        if vgg_feat is not None:
+            sem = A.vq_semantic(zq, self.conv_semantic[0].weight, self.conv_semantic[0].bias, vgg_feat)
+            qloss = qloss + self.semantic_weight * sem
+            self.last_semantic = sem.detach()
         quant2 = A.conv2d_small(zq, self.post_quant_conv.weight, self.post_quant_conv.bias, layout="nhwc", out_f32=True)
         xrec, _ = self.decoder.train_nhwc(quant2)
         self.last_indices = idx

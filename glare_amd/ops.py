@@ -145,6 +145,43 @@ def vq_restart_ema(window, z_tokens, codebook, embed_avg, cluster_size, offset, 
     return out[0], out[1]
 
 
+def vq_semantic(quant, weight, bias, feat):
+    """The semantic guidance term, fused (VQModel_arch.py:85-88; csrc/vq_semantic.hip): quant fp32 [N,3] (or [..,3]), weight fp32 [256,3]
+    (or conv_semantic's [256,3,1,1]), bias fp32 [256], feat 16-bit [N,256] of the current precision -> (loss fp32 [1] =
+    mse(relu(W q + b), feat), dq fp32 like quant, dW fp32 [256,3], db fp32 [256]): the three gradients of that loss, from one read of feat.
+    N <= 2^24.  No atomics, the same bits on every run."""
+    require_cuda(quant, weight, bias, feat)
+    cout = bias.numel()
+    assert quant.dtype == torch.float32 and quant.shape[-1] == 3 and quant.numel() > 0, (quant.dtype, tuple(quant.shape))
+    assert weight.dtype == torch.float32 and weight.numel() == cout * 3 and bias.dtype == torch.float32, (weight.dtype, tuple(weight.shape))
+    n = quant.numel() // 3
+    assert feat.dtype == act_dtype() and feat.numel() == n * cout and feat.shape[-1] == cout, (feat.dtype, tuple(feat.shape), n, cout)
+    assert quant.device == weight.device == bias.device == feat.device
+    quant, weight, bias, feat = quant.contiguous(), weight.contiguous(), bias.contiguous(), feat.contiguous()
+    lib = _lib.lib()
+    nws = lib.glare_vq_semantic_workspace_bytes(n, cout)
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=quant.device)
+    loss = torch.empty(1, dtype=torch.float32, device=quant.device)
+    dq, dw, db = torch.empty_like(quant), torch.empty(cout, 3, dtype=torch.float32, device=quant.device), torch.empty_like(bias)
+    check(lib.glare_vq_semantic_bf16(ptr(quant), ptr(weight), ptr(bias), ptr(feat), n, cout, ptr(loss), ptr(dq), ptr(dw), ptr(db), ptr(ws), nws,
+                                     stream_handle()), "glare_vq_semantic_bf16")
+    return loss, dq, dw, db
+
+
+def vq_semantic_scale(g, dq_unit, dw_unit=None, db_unit=None):
+    """g: fp32 [1] on the device, the upstream gradient of vq_semantic's loss -> (g dq_unit, g dw_unit, g db_unit) in one launch, no host
+    read; dw_unit / db_unit None: that product is None."""
+    require_cuda(g, dq_unit, dw_unit, db_unit)
+    assert g.dtype == torch.float32 and g.numel() == 1 and g.device == dq_unit.device, (g.dtype, tuple(g.shape))
+    assert dq_unit.dtype == torch.float32 and dq_unit.shape[-1] == 3 and dq_unit.is_contiguous() and dq_unit.numel() > 0
+    for t, shape in ((dw_unit, (256, 3)), (db_unit, (256,))):
+        assert t is None or (t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == g.device), shape
+    dq, dw, db = (None if t is None else torch.empty_like(t) for t in (dq_unit, dw_unit, db_unit))
+    check(_lib.main_lib().glare_vq_semantic_scale_f32(ptr(g.contiguous()), dq_unit.numel() // 3, ptr(dq_unit), ptr(dw_unit), ptr(db_unit), ptr(dq),
+                                                      ptr(dw), ptr(db), stream_handle()), "glare_vq_semantic_scale_f32")
+    return dq, dw, db
+
+
 # ---- convolution --------------------------------------------------------------------------------
 # Every constant and both structs of this section are read from include/glare_hip.h (_lib.constants(), _lib.structs()).
 _K = _lib.constants()

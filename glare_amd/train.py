@@ -278,6 +278,7 @@ GAN_TERMS = ("g_loss", "d_weight", "d_loss")
 USAGE_TERMS = ("codebook_active", "codebook_perplexity")      # Stage1Trainer(codebook_usage=True)
 RESTART_KEY = "codebook_restart"   # Stage1Trainer(codebook_restart=P): {"window": int64 [K], "every": P, "threshold": T}, one more key of a `.state` file
 RESTART_TERMS = ("codebook_restarted",)
+SEMANTIC_TERMS = ("semantic_loss",)                            # Stage1Trainer(semantic=...): the semantic guidance part of codebook_loss
 RESTART_OFFSET_STEP = 7919         # the r-th restart of a run takes its tokens from offset r * 7919 (a prime: successive restarts start apart)
 
 
@@ -529,7 +530,8 @@ class Stage1Trainer(Trainer):
 
     def __init__(self, net, lr_G=1e-4, weight_decay_G=0.0, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0,
                  device_state=False, precision="fp16", discriminator=None, disc_start=10000, disc_weight=0.8, disc_factor=1.0,
-                 codebook_usage=False, codebook_restart=0, restart_threshold=0, codebook_ema=None, ema_eps=1e-5):
+                 codebook_usage=False, codebook_restart=0, restart_threshold=0, codebook_ema=None, ema_eps=1e-5, semantic=None,
+                 semantic_weight=0.1):
         """lr_G: a starting point, not a tuned value (the reference sets `self.learning_rate` from a config it does not ship).
         discriminator: an NLayerDiscriminator on the net's device, or None (no GAN term: the step and every file are what they were);
         disc_start / disc_weight / disc_factor: taming's defaults for the VQGAN configs.
@@ -560,7 +562,21 @@ class Stage1Trainer(Trainer):
         about eps and its row embed_avg / ~eps, far from every latent, and it stays dead.  So use it with codebook_restart: on the restart
         steps, AFTER that step's EMA update, ops.vq_restart_ema re-seeds codebook and embed_avg rows alike and sets their cluster_size to
         1.0.  Both tensors travel in the `.state` file with d and eps; a resume under other values, or with the key and the option not
-        both present, is refused.  <iter>_VQ.pth keeps VQModel's keys."""
+        both present, is refused.  <iter>_VQ.pth keeps VQModel's keys.
+        semantic: a loaded losses.SemanticTarget (VGG19 down to relu3_4, the caller's file: losses.load_vgg19), or None (the default) --
+        off: nothing new is launched, and the step and every file are what they were, bit for bit.  On: the reference's semantic guidance
+        term (VQModel_arch.py:85-88, `emb_loss += 0.1 * F.mse_loss(conv_semantic(quant), vgg_feat)`; fed as the ancestor's HQ pre-training
+        stage feeds it, the extractor on the input under no_grad).  Both step forms compute vgg_feat = semantic(x) once per step and hand it
+        to VQModel.train_nhwc, where the term rides in qloss -- so codebook_weight multiplies it as it multiplies emb_loss there, and the
+        GAN step needs nothing else.  `last_terms["codebook_loss"]` is reported as it is computed, INCLUDING the term;
+        `last_terms["semantic_loss"]` = codebook_weight * semantic_weight * mse is the part of it (not a further summand of the total).
+        `conv_semantic.*` is then NOT declared never_used for this trainer: it trains in the same Adam group (the flat layout always held
+        it, so the `.state` layout does not change).  The reference's configure_optimizers list (:150-155) omits conv_semantic because the
+        branch is dead there (its forward passes no vgg_feat); the ancestor optimises all of net_g.  The term's gradient reaches the
+        encoder and quant_conv through the straight-through output and never a codebook row, so it goes together with codebook_ema,
+        codebook_restart, the discriminator and LPIPS.  The loss network is in no checkpoint: objective_tag() names it with its weight, and
+        a resume under another objective is refused."""
+        self.semantic, self.semantic_weight = semantic, float(semantic_weight)
         self.codebook_usage = bool(codebook_usage)
         self.codebook_ema, self.ema_eps = (None if codebook_ema is None else float(codebook_ema)), float(ema_eps)
         assert self.codebook_ema is None or (0.0 < self.codebook_ema < 1.0 and self.ema_eps >= 0.0), (codebook_ema, ema_eps)
@@ -571,13 +587,15 @@ class Stage1Trainer(Trainer):
         for p in net.parameters():
             p.requires_grad_(True)
         named = list(net.named_parameters())
-        never = [p for n, p in named if n.startswith(STAGE1_NEVER_USED)]
+        never = [] if semantic is not None else [p for n, p in named if n.startswith(STAGE1_NEVER_USED)]
         E = net.quantize.embedding.weight
         if self.codebook_ema is not None:            # in the flat layout as ever (one `.state` layout), outside what Adam updates
             never.append(E)
         super().__init__(net.train(), [p for n, p in named if not n.startswith(STAGE1_NEVER_USED)], precision, [p for _, p in named], lr_G,
                          weight_decay_G, never_used=never, betas=(0.5, 0.9))
         self.net = self.netG                         # `netG`: the name the driver and the checkpoint code read
+        if semantic is not None:
+            net.semantic_weight = self.semantic_weight
         self.discriminator, self.opt_d = discriminator, None
         self.disc_start, self.disc_weight, self.disc_factor = int(disc_start), float(disc_weight), float(disc_factor)
         self.global_step = 0                         # Lightning's global_step: steps taken so far (on_resume restores it)
@@ -660,9 +678,23 @@ class Stage1Trainer(Trainer):
     def on_resume(self, step):
         self.global_step = step                      # what `disc_start` and the restart's period are compared with
 
+    def objective_tag(self):
+        tags = [t for t in (Trainer.objective_tag(self), None if self.semantic is None else
+                            "%s x %g" % (type(self.semantic).__name__, self.semantic_weight)) if t is not None]
+        return " + ".join(tags) or None
+
     def log_terms(self):
-        return ((GAN_TERMS if self.discriminator is not None else ()) + super().log_terms() + (USAGE_TERMS if self.codebook_usage else ())
-                + (RESTART_TERMS if self.codebook_restart else ()))
+        return ((GAN_TERMS if self.discriminator is not None else ()) + super().log_terms() + (SEMANTIC_TERMS if self.semantic is not None else ())
+                + (USAGE_TERMS if self.codebook_usage else ()) + (RESTART_TERMS if self.codebook_restart else ()))
+
+    def _forward(self, gt):
+        """The taped autoencoder on the step's batch; with the semantic term, its target first: (xrec, qloss, idx)."""
+        if self.semantic is None:
+            return self.net.train_nhwc(gt)
+        return self.net.train_nhwc(gt, self.semantic(ops.nchw_to_nhwc(gt, bf16=False)))
+
+    def _semantic_terms(self):
+        return {} if self.semantic is None else {"semantic_loss": self.net.last_semantic * (self.codebook_weight * self.semantic_weight)}
 
     def _usage_terms(self, idx):
         """{codebook_active, codebook_perplexity} of one forward pass's indices, device tensors.  With the restart on, the same
@@ -713,11 +745,12 @@ class Stage1Trainer(Trainer):
         with ops.use_precision(self.precision):
             self.opt.zero_grad()
             with self.pack_cache:
-                xrec, qloss, idx = self.net.train_nhwc(gt)
+                xrec, qloss, idx = self._forward(gt)
                 loss, self.last_terms = stage1_loss(xrec, gt, qloss, self.codebook_weight, self.perceptual, self.perceptual_weight)
                 self.opt.scale_loss(loss).backward()
             self.opt.step()
         self.net.invalidate()                        # packed inference weights are stale now
+        self.last_terms.update(self._semantic_terms())
         self.last_terms.update(self._codebook_terms(idx))     # (the search reads embedding.weight itself: nothing packed goes stale)
         if self.discriminator is not None:           # before disc_start: f = 0, nothing of D launched, its parameters and optimizer untouched
             self.last_terms.update(g_loss=self._zero, d_weight=self._zero, d_loss=self._zero)
@@ -737,7 +770,7 @@ class Stage1Trainer(Trainer):
             self.opt_d.zero_grad()
             self.opt_d.state3[2:3].copy_(self.opt.state3[2:3])       # D's lr follows the generator's schedule (one device scalar)
             with self.pack_cache:
-                xrec, qloss, idx = self.net.train_nhwc(gt)
+                xrec, qloss, idx = self._forward(gt)
                 # the two gradients at xrec, on a detached leaf: nll's and, through D (data gradients only), g_loss's.  Both carry the
                 # generator's loss scale s (fp16: 1 / n of a mean is an fp16 subnormal unscaled), divided out of the norms below
                 xr = xrec.detach().requires_grad_(True)
@@ -768,6 +801,7 @@ class Stage1Trainer(Trainer):
         loss = nll.detach() + d_weight * f * g_loss.detach() + cb.detach()
         terms["codebook_loss"] = cb
         terms.update(g_loss=g_loss.detach(), d_weight=d_weight, d_loss=d_loss.detach())
+        terms.update(self._semantic_terms())
         terms.update(self._codebook_terms(idx))
         self.last_terms = terms
         return loss

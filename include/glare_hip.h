@@ -1044,6 +1044,30 @@ int glare_lpips_head_backward_bf16(const void* a, const void* b, const float* w,
 int glare_image_affine_f32(const float* x, const float* mul, const float* add_or_null, float* y, long long n_pixels, int C,
                            glare_stream_t stream);
 
+/* ---- stage 1, semantic guidance: the codes through conv_semantic against VGG19 relu3_4 (csrc/vq_semantic.hip) -----------------------
+ * Replaces `F.mse_loss(self.conv_semantic(quant), vgg_feat)` of VQModel.decode (code/models/modules/VQModel_arch.py:85-88; conv_semantic =
+ * Conv2d(3, 256, 1) + ReLU, :56-61) and what autograd derives from it, in ONE pass over the feature map: the [n_tokens][256] activation
+ * is never stored.  quant [n_tokens][3], weight [256][3], bias [256] fp32; feat dense 16-bit [n_tokens][256] (NHWC), 8-byte aligned, constant.
+ *   pre_tc = ((W_c0 q_t0 + W_c1 q_t1) + W_c2 q_t2) + b_c     d_tc = relu(pre_tc) - feat_tc     e_tc = d_tc [pre_tc > 0]  (0 at pre == 0, as torch)
+ *   loss_out[0] = k / 2 sum_tc d_tc^2          k = 2 / (n_tokens * 256), formed in fp64 on the host and rounded to fp32 once
+ *   dq [n_tokens][3] = k sum_c e_tc W_cj       dW [256][3] = k sum_t e_tc q_tj       db [256] = k sum_t e_tc       (the gradients of loss_out)
+ * All arithmetic and accumulation fp32, one rounding per operation as written.  No atomics; every sum has one order that depends on n_tokens
+ * alone (bitwise reproducible): chunk = ceil(n_tokens / min(512, ceil(n_tokens / 64))) consecutive tokens per workgroup, groups =
+ * ceil(n_tokens / chunk); within one, wave w of 4 takes tokens t0 + w, t0 + w + 4, ...; a lane owns 4 consecutive channels.  dq: the lane's 4
+ * channels in order, then the xor-shuffle tree of the wave.  dW, db, loss: the wave's tokens in order (loss: (token, channel) order per lane,
+ * then the shuffle tree), the 4 waves in order, then the workgroups by a second launch over the partial rows in the workspace: the workgroup
+ * axis in 8 slices of ceil(groups / 8), each in workgroup order, then the 8 slices in slice order.
+ * workspace: glare_vq_semantic_workspace_bytes(n_tokens, cout) bytes (0: not a size the kernel takes).  n_tokens <= 2^24.
+ * GLARE_ERR_INVALID: a null pointer, n_tokens <= 0, cout <= 0, feat not 8-byte aligned; GLARE_ERR_UNSUPPORTED: cout != 256, n_tokens > 2^24;
+ * GLARE_ERR_WORKSPACE: a null or short workspace -- all before any launch.
+ * glare_vq_semantic_scale_f32: dq = g dq_unit, dW = g dW_unit, db = g db_unit in ONE launch, g = g_dev[0] read on the device (the upstream
+ *   gradient of the loss: the term's weights and, under fp16, the loss scale), one rounding each.  dW / db NULL: not written. */
+size_t glare_vq_semantic_workspace_bytes(long long n_tokens, int cout);
+int glare_vq_semantic_bf16(const float* quant, const float* weight, const float* bias, const void* feat, long long n_tokens, int cout,
+                           float* loss_out, float* dq, float* dW, float* db, void* workspace, size_t workspace_bytes, glare_stream_t stream);
+int glare_vq_semantic_scale_f32(const float* g_dev, long long n_tokens, const float* dq_unit, const float* dW_unit, const float* db_unit,
+                                float* dq, float* dW, float* db, glare_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
