@@ -26,6 +26,7 @@ scikit-image is not available to pin what it computed; stage 3's `SSIM` column i
 Rows are written in dataset order (the reference prepends each new row).  Without checkpoints the weights are name-seeded.
 
     python -m glare_amd.evaluate stage1 --run RUN --root LOLdataset [...]          (no --net-vq: the run's own files are the VQGAN)
+    python -m glare_amd.evaluate stage3 --run RUN --root LOLdataset --ema          (the averaged weights of `fit --weights-ema`: *_G_ema.pth)
 
 scores every `RUN/models/*_VQ.pth` of `glare_amd.fit stage1`, the file `--net-vq` takes everywhere else, by the prior's own
 reconstruction of the ground truth (stage1_reconstruct, the protocol of fit.make_validate_stage1): pad bottom / right by symmetric
@@ -53,6 +54,8 @@ COLUMNS = {"stage1": ("PSNR", "SSIM", "codes", "LPIPS"), "stage2": ("Adjust_PSNR
 LEAD = {"stage1": ("conf", "name"), "stage2": ("conf", "heat", "name"), "stage3": ("conf", "name")}
 CHECKPOINT_TAG = {"stage1": "VQ", "stage2": "G", "stage3": "G"}       # <iter>_<tag>.pth: what glare_amd.fit writes for the stage
 LOWER_IS_BETTER = ("LPIPS", "Adjust_LPIPS")
+NO_EMA_FILES = ("--ema: %s holds no *_%s_ema.pth: the averaged weights are written by a run trained with `glare_amd.fit ... --weights-ema DECAY`; "
+                "without --ema the run's own weights are scored")
 NET_VQ_REFUSAL = "--net-vq is not a stage1 option: the run's own <iter>_VQ.pth files are the VQGAN that is scored"
 WARM_SIDE = 32          # the side of the one-image pass that rebuilds every packed filter after a checkpoint swap
 
@@ -235,11 +238,12 @@ def score_checkpoint(stage, netG, net_hq, lows, gts, batch=8, precision=None, lp
 
 
 # ---- the sweep ----------------------------------------------------------------------------------------------------------------
-def list_checkpoints(run_or_files, stage="stage2"):
+def list_checkpoints(run_or_files, stage="stage2", ema=False):
     """A run folder -> its models/*_G.pth (stage1: *_VQ.pth) in natural order (natsorted(os.listdir(.../models)), test_stage2.py:110);
-    a list of files -> the same order."""
+    a list of files -> the same order.  ema: the averaged weights of `glare_amd.fit --weights-ema` instead, models/*_G_ema.pth (*_VQ_ema.pth):
+    the two sets never mix, neither glob matches the other's names."""
     if isinstance(run_or_files, (str, os.PathLike)):
-        files = glob.glob(os.path.join(run_or_files, "models", "*_%s.pth" % CHECKPOINT_TAG[stage]))
+        files = glob.glob(os.path.join(run_or_files, "models", "*_%s%s.pth" % (CHECKPOINT_TAG[stage], "_ema" if ema else "")))
     else:
         files = list(run_or_files)
     return sorted(files, key=natural_key)
@@ -410,9 +414,16 @@ def main(argv=None):
                     help="16-bit format of activations and filters (default fp16; images whose fp16 output is not finite are re-run in bf16)")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--save-images", action="store_true", help="write the scored uint8 images under <out>/<name>/")
+    ap.add_argument("--ema", action="store_true", help="score the averaged weights of a run trained with --weights-ema, <run>/models/<iter>_G_ema.pth "
+                                                        "(stage1: <iter>_VQ_ema.pth), instead; the default output folder is <run>/results-<stage>-ema")
     args = ap.parse_args(argv)
     if args.stage == "stage1" and args.net_vq:
         ap.error(NET_VQ_REFUSAL)
+    run = args.run
+    if args.ema:
+        run = list_checkpoints(args.run, args.stage, ema=True)
+        if not run:
+            ap.error(NO_EMA_FILES % (os.path.join(args.run, "models"), CHECKPOINT_TAG[args.stage]))
     import torch
 
     if args.select not in columns(args.stage, args.lpips):
@@ -428,7 +439,7 @@ def main(argv=None):
 
         lpips_net = metrics.build_lpips_alex(args.lpips_weights, device)
     nets = build_nets(args.stage, args.net_vq, device)
-    res = sweep(args.stage, args.run, args.out or os.path.join(args.run, "results-%s" % args.stage), lows, gts, names, nets, args.select,
+    res = sweep(args.stage, run, args.out or os.path.join(args.run, "results-%s%s" % (args.stage, "-ema" if args.ema else "")), lows, gts, names, nets, args.select,
                 args.precision, max(1, args.batch), lpips_net, args.save_images, device=device)
     print(json.dumps(res))
     return res

@@ -11,6 +11,7 @@ code/train_stage3.py:138-300 over models/base_model.py:46-83 and models/lr_sched
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-restart 100  (every 100 steps, re-seed the codes nothing selected)
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --codebook-ema 0.99 --codebook-restart 100   (an EMA codebook, no gradient)
     python -m glare_amd.fit stage1 --root LOLdataset --out prior --vgg19 vgg19-dcbb9e9d.pth [--semantic-weight 0.1]   (semantic guidance)
+    python -m glare_amd.fit stage3 --root LOLdataset --out run --net-g stage2_G.pth --net-vq vqgan.pkl --weights-ema 0.999   (averaged weights)
 
 Stage 1 trains the VQGAN prior itself (VQModel_arch.py:98-101, 148-157) on the ground-truth half of the pairs and writes
 <out>/models/<iter>_VQ.pth under the reference's VQModel key names: what `--net-vq` of stages 2 and 3, `evaluate` and `enhance` load.
@@ -20,6 +21,10 @@ are written to no checkpoint: a resumed run names the same files again (the .sta
 without it, or with another --perceptual-weight, is refused).
 --vgg19 adds stage 1's semantic guidance term (VQModel_arch.py:85-88: the codes through conv_semantic against VGG19 relu3_4 of the input)
 from the user's VGG19 file (losses.load_vgg19, strict); the same rules hold for it: frozen, in no checkpoint, named again on a resume.
+--weights-ema keeps an exponential moving average of the trained weights on the device (every stage; BaseModel.model_ema of the stage-1
+lineage, basicsr/models/base_model.py:85-92): every checkpoint gains <iter>_G_ema.pth (stage 1: <iter>_VQ_ema.pth), a plain state dict under
+the network's own key names, every validation a second result `val_ema` scored under the averaged weights, and a resume continues the
+average from that file (and is refused, by the file's name, where it is missing).
 The reference ships no stage-1 configuration (its prior is a download): `lr_G` 1e-4 is a starting point, not a tuned value.
 
 What is mirrored: the option keys and their per-stage values, the seeding, the index order of the reference's DataLoader, the
@@ -278,6 +283,9 @@ def fit(options, trainer, dataset, out_dir, step_fn=None, batch_fn=None, resume=
             if validate_fn is not None and ((val_freq and step % val_freq == 0) or step == niter):
                 rec = rec or {"epoch": epoch, "iter": step, "lr": lr}
                 rec["val"] = validate_fn(step)
+                if trainer.weights_ema is not None:         # the same score under the averaged weights
+                    with trainer.ema_weights():
+                        rec["val_ema"] = validate_fn(step)
             if step % save_freq == 0 or step == niter:
                 save(epoch, step, order, done)
                 saved_at = step
@@ -329,6 +337,12 @@ def check_restart_options(stage, codebook_restart=0, restart_threshold=None):
         raise ValueError("--restart-threshold is a token count (a code is dead at <= that many selections in a window), not %d" % restart_threshold)
 
 
+def check_weights_ema_option(weights_ema=None):
+    """The refusal of --weights-ema: ValueError with the reason, before anything is built."""
+    if weights_ema is not None and not 0.0 <= float(weights_ema) < 1.0:
+        raise ValueError(WEIGHTS_EMA_REFUSAL % (weights_ema,))
+
+
 def check_ema_options(stage, codebook_ema=None, ema_eps=None):
     """The refusals of --codebook-ema / --ema-eps: ValueError with the reason, before anything is built."""
     if stage != "stage1" and (codebook_ema is not None or ema_eps is not None):
@@ -367,14 +381,14 @@ def build_semantic(device, vgg19=None):
 
 def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, precision="fp16", gan=False, net_d=None, vgg16=None,
                   lpips_heads=None, perceptual_weight=None, codebook_usage=False, codebook_restart=0, restart_threshold=None,
-                  codebook_ema=None, ema_eps=None, vgg19=None, semantic_weight=None):
+                  codebook_ema=None, ema_eps=None, vgg19=None, semantic_weight=None, weights_ema=None):
     """Networks (name-seeded unless checkpoint files are given, as glare_amd.infer) and the stage's trainer.  gan (stage 1 only): with the
     patch discriminator (taming's initialisation under the run's seed, or the `_D.pth` file net_d).  vgg16 / lpips_heads: the weight
     files of the perceptual term (stage 1: LPIPS, both files; stage 3: the VGG16-feature loss, the backbone alone); perceptual_weight:
     stage 1's factor on it (default 1.0).  The loss network is frozen and is written to no checkpoint: a resumed run names the files again.
     codebook_usage, codebook_restart / restart_threshold, codebook_ema / ema_eps (stage 1 only): Stage1Trainer's; off, the trainer is built
     without the keywords.  vgg19 / semantic_weight (stage 1 only): the VGG19 file of the semantic guidance term and its factor (default 0.1);
-    frozen and in no checkpoint like the perceptual network."""
+    frozen and in no checkpoint like the perceptual network.  weights_ema (every stage): Trainer's decay of the averaged weights."""
     from . import modules as M
 
     check_perceptual_options(stage, vgg16, lpips_heads, perceptual_weight)
@@ -389,6 +403,8 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
         raise ValueError(CODEBOOK_USAGE_REFUSAL)
     check_restart_options(stage, codebook_restart, restart_threshold)
     check_ema_options(stage, codebook_ema, ema_eps)
+    check_weights_ema_option(weights_ema)
+    averaged = {} if weights_ema is None else {"weights_ema": float(weights_ema)}
     netG, net_hq = checkpoint.build_nets(stage, True, net_g, net_vq, options, device)
     if stage == "stage1":
         disc = None
@@ -409,12 +425,13 @@ def build_trainer(stage, options, device, net_g=None, net_vq=None, graph=False, 
                                    **({"codebook_ema": float(codebook_ema), "ema_eps": 1e-5 if ema_eps is None else float(ema_eps)}
                                       if codebook_ema is not None else {}),
                                    **({"semantic": build_semantic(device, vgg19),
-                                       "semantic_weight": 0.1 if semantic_weight is None else float(semantic_weight)} if vgg19 else {}))
+                                       "semantic_weight": 0.1 if semantic_weight is None else float(semantic_weight)} if vgg19 else {}),
+                                   **averaged)
     if stage == "stage2":
         return train.Stage2Trainer(netG, net_hq, lr_G=tr["lr_G"], lr_RRDB=tr.get("lr_RRDB"), weight_decay_G=tr.get("weight_decay_G", 0),
-                                   train_rrdb=bool(options["network_G"].get("train_RRDB", False)), precision=precision)
+                                   train_rrdb=bool(options["network_G"].get("train_RRDB", False)), precision=precision, **averaged)
     return train.Stage3Trainer(netG, net_hq, lr_G=tr["lr_G"], weight_decay_G=tr.get("weight_decay_G", 0), precision=precision,
-                               perceptual=perceptual)
+                               perceptual=perceptual, **averaged)
 
 
 CODEBOOK_USAGE_REFUSAL = ("--codebook-usage is a stage1 option: stage1 is the stage that trains the codebook (stages 2 and 3 read a frozen one; "
@@ -425,6 +442,7 @@ CODEBOOK_EMA_REFUSAL = ("--codebook-ema / --ema-eps are stage1 options: stage1 i
                         "frozen one, which nothing updates)")
 SEMANTIC_REFUSAL = ("--vgg19 / --semantic-weight are stage1 options: the semantic guidance term belongs to the VQGAN prior's codebook loss "
                     "(VQModel_arch.py:85-88); stages 2 and 3 read a frozen prior")
+WEIGHTS_EMA_REFUSAL = ("--weights-ema takes the decay of the moving average of the trained weights, a number in [0, 1) such as 0.999, not %r")
 GAN_REFUSAL = "--gan is a stage1 option: the patch discriminator belongs to the VQGAN prior's objective (stages 2 and 3 train no GAN term)"
 LPIPS_REFUSAL = ("stage1's perceptual term is LPIPS and needs both files: --vgg16 (the VGG16 backbone) and --lpips-heads (the five linear "
                  "heads, taming's / the lpips package's vgg.pth); one without the other would leave half the network at its initialisation")
@@ -551,6 +569,9 @@ def parse_args(argv=None):
                     help="stage1: move the codebook by an exponential moving average of the latents that select each code (decay in (0, 1), "
                          "e.g. 0.99) instead of its gradient; use with --codebook-restart, a code nothing selects is thrown far away")
     ap.add_argument("--ema-eps", type=float, default=None, metavar="EPS", help="--codebook-ema: the smoothing of the cluster sizes (default 1e-5)")
+    ap.add_argument("--weights-ema", type=float, default=None, metavar="DECAY",
+                    help="keep an exponential moving average of the trained weights on the device (decay in [0, 1), e.g. 0.999): every checkpoint "
+                         "gains <iter>_G_ema.pth (stage1: <iter>_VQ_ema.pth) and every validation `val_ema`")
     ap.add_argument("--no-val", action="store_true", help="skip the closing validation")
     args = ap.parse_args(argv)
     if args.codebook_usage and args.stage != "stage1":
@@ -564,6 +585,7 @@ def parse_args(argv=None):
     try:
         check_restart_options(args.stage, args.codebook_restart, args.restart_threshold)
         check_ema_options(args.stage, args.codebook_ema, args.ema_eps)
+        check_weights_ema_option(args.weights_ema)
         check_perceptual_options(args.stage, args.vgg16, args.lpips_heads, args.perceptual_weight)
         check_semantic_options(args.stage, args.vgg19, args.semantic_weight)
     except ValueError as e:
@@ -589,7 +611,7 @@ def main(argv=None):
     assert torch.cuda.is_available(), "glare_amd.fit needs an MI355X: the HIP kernels are the only implementation"
     device = torch.device("cuda", 0)
     net_g, net_vq, net_d = args.net_g, args.net_vq, None
-    resume = None
+    resume, net_ema = None, None
     if args.resume:
         resume = torch.load(args.resume, map_location="cpu", weights_only=False)
         models = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(args.resume))), "models")
@@ -598,13 +620,20 @@ def main(argv=None):
             net_d = os.path.join(models, "%d_D.pth" % resume["iter"]) if args.gan else None
         elif net_g is None:
             net_g = os.path.join(models, "%d_G.pth" % resume["iter"])
+        if args.weights_ema is not None:      # the average continues from the file written beside the weights
+            net_ema = os.path.join(models, "%d_%s%s.pth" % (resume["iter"], "VQ" if args.stage == "stage1" else "G", train.EMA_SUFFIX))
+            if not os.path.exists(net_ema):
+                raise ValueError(train.EMA_RESUME_REFUSAL % net_ema)
     train_opt = dict(options["datasets"]["train"], root=args.root)
     host_ds = D.LAYOUTS[args.layout](train_opt, train=True, all_opt=options)
     dataset = D.DeviceLoLDataset(host_ds, device)
     trainer = build_trainer(args.stage, options, device, net_g, net_vq, args.graph, args.precision, gan=args.gan, net_d=net_d,
                             vgg16=args.vgg16, lpips_heads=args.lpips_heads, perceptual_weight=args.perceptual_weight,
                             codebook_usage=args.codebook_usage, codebook_restart=args.codebook_restart, restart_threshold=args.restart_threshold,
-                            codebook_ema=args.codebook_ema, ema_eps=args.ema_eps, vgg19=args.vgg19, semantic_weight=args.semantic_weight)
+                            codebook_ema=args.codebook_ema, ema_eps=args.ema_eps, vgg19=args.vgg19, semantic_weight=args.semantic_weight,
+                            weights_ema=args.weights_ema)
+    if net_ema:
+        trainer.load_ema_weights(net_ema)
     if args.vgg16:        # the opening line of a run with a perceptual term: which files it was built from
         print(json.dumps({"perceptual": type(trainer.perceptual).__name__, "vgg16": args.vgg16, "lpips_heads": args.lpips_heads,
                           "tensors_loaded": len(trainer.perceptual.loaded_keys)}), flush=True)

@@ -14,6 +14,9 @@ and their .grad are views), so the optimizer is ONE kernel launch per group and 
 RCCL all-reduce per group over xGMI (106 MB at stage 2) instead of nn.DataParallel's per-step replicate / scatter /
 gather through GPU 0 (LLFlow_model.py:72-75).
 """
+import contextlib
+import os
+
 import torch
 import torch.distributed as dist
 
@@ -182,11 +185,22 @@ class FlatAdam:
     GradScaler's found_inf / scale / growth tracker: a step has no host-side state and no host synchronisation (the Python launch
     loop runs ahead of the GPU; the whole step replays from a hipGraph, GraphedStep).  `device_state` is accepted and ignored (Trainer)."""
 
-    def __init__(self, groups, betas=(0.9, 0.999), eps=1e-8, device_state=True, loss_scaling=False):
+    def __init__(self, groups, betas=(0.9, 0.999), eps=1e-8, device_state=True, loss_scaling=False, weights_ema=None):
         """loss_scaling: fp16 training -- `scale_loss()` multiplies the loss by the scale before backward and step() divides it out
         of the gradients (scaler.scale / scaler.unscale_, LLFlow_model.py:236-241); bf16 training keeps fp32's range and only runs
-        the scaler's bookkeeping."""
+        the scaler's bookkeeping.
+        weights_ema: a decay d in [0, 1) keeps an exponential moving average of every group's weights on the device (BaseModel.model_ema,
+        basicsr/models/base_model.py:85-92; csrc/weight_ema.hip); None (the default) is off: nothing is allocated or launched, and a step is
+        what it was, bit for bit.  On: each non-empty group gets `ema` (fp32, the size of `w`) and the optimizer `ema_seeded` (int32 [1], 0).
+        At the end of EVERY step(), skipped by the GradScaler or not (the weights did not move then and the average keeps decaying toward
+        them, as model_ema called every iteration does), one launch per group over the WHOLE buffer: ema_1 = w_1, the weights after the
+        first step (a fresh flow's data-dependent ActNorm initialisation is inside the seed), ema_t = d ema_{t-1} + (1 - d) w_t after
+        that; then the flag is filled with 1 on the device, so a captured step holds the same launches on every replay.  The average of a
+        parameter Adam never updates is that parameter, up to the rule's own roundings (Trainer.ema_state_dict takes those live).  Ranks
+        hold identical weights: no communication."""
         self.groups, self.betas, self.eps = groups, betas, eps
+        self.weights_ema = None if weights_ema is None else float(weights_ema)
+        assert self.weights_ema is None or 0.0 <= self.weights_ema < 1.0, weights_ema
         self.loss_scaling = bool(loss_scaling)
         dev = next(g.w.device for g in groups if g.w.numel())
         # GradScaler's state (torch.cuda.amp.GradScaler defaults, LLFlow_model.py:120): found_inf of the step in progress, the
@@ -197,6 +211,18 @@ class FlatAdam:
         self.growth_factor, self.backoff_factor, self.growth_interval = 2.0, 0.5, 2000
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.state3 = torch.tensor([1.0, 1.0, 1.0], dtype=torch.float32, device=dev)   # bc1, sqrt(bc2), lr multiplier
+        self.ema_seeded = None
+        if self.weights_ema is not None:
+            for g in groups:
+                if g.w.numel():
+                    g.ema = torch.empty_like(g.w)          # holds nothing until the first step seeds it (ema_seeded)
+            self.ema_seeded = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def ema_tensors(self):
+        """Every tensor the weight average lives in (GraphedStep snapshots them around its warm-up steps); [] when it is off."""
+        if self.weights_ema is None:
+            return []
+        return [g.ema for g in self.groups if g.w.numel()] + [self.ema_seeded]
 
     @property
     def t(self):
@@ -244,6 +270,11 @@ class FlatAdam:
                                          g.weight_decay, 1.0 / world, self.found_inf, self.scale if self.loss_scaling else None)
         T.gradscaler_update_(self.scale, self.growth_tracker, self.found_inf, self.growth_factor, self.backoff_factor,
                              self.growth_interval)
+        if self.weights_ema is not None:           # on skipped steps too: no host decision, the same launches every step
+            for g in self.groups:
+                if g.w.numel():
+                    T.weight_ema_(g.ema, g.w, self.weights_ema, self.ema_seeded)
+            self.ema_seeded.fill_(1)
 
     def last_step_skipped(self):
         return bool(int(self.found_inf.item()))
@@ -313,14 +344,28 @@ def exchange_ema_stats(stats, n_tokens=None):
 
 
 def two_group_adam(params, lr, weight_decay, never_used=(), second=(), second_lr=None, second_weight_decay=0.0, betas=(0.9, 0.999),
-                   precision="fp16"):
+                   precision="fp16", weights_ema=None):
     """FlatAdam in the layout of the reference's optimizer: always the two groups [other, RRDB] (LLFlow_model.py:110-118,
     VQLLFLOWD_model.py:113-121).  The second group is EMPTY wherever the conditional encoder is not trained (stage 2 with train_RRDB:
     false / before train_RRDB_delay, stage 3, and stage 1 and its discriminator, which have no such encoder), exactly as in the
-    reference's optimizer -- so `.state` files are interchangeable (glare_amd/checkpoint.py).  fp16 scales the loss."""
+    reference's optimizer -- so `.state` files are interchangeable (glare_amd/checkpoint.py).  fp16 scales the loss.  weights_ema: FlatAdam's."""
     return FlatAdam([FlatGroup(params, lr, weight_decay, never_used=never_used),
                      FlatGroup(second, lr if second_lr is None else second_lr, second_weight_decay, device=params[0].device)],
-                    betas=betas, loss_scaling=precision == "fp16")
+                    betas=betas, loss_scaling=precision == "fp16", weights_ema=weights_ema)
+
+
+WEIGHTS_EMA_KEY = "weights_ema"    # Trainer(weights_ema=d): {"decay": d}, one more key of a `.state` file (the average itself is a network file)
+EMA_SUFFIX = "_ema"                # <iter>_<checkpoint_tag>_ema.pth
+EMA_RESUME_REFUSAL = ("--weights-ema: %s does not exist: a resumed run continues the average from the file written beside the weights (the "
+                      ".state file was written without --weights-ema, or the file was removed); resume without --weights-ema, or put the file back")
+EMA_UNSEEDED_REFUSAL = "ema_weights(): no step has seeded the average yet (it starts as the weights after the first step)"
+
+
+class _AveragedNetwork:
+    """What checkpoint.save_network needs of a network, over a trainer's averaged weights."""
+
+    def __init__(self, trainer):
+        self.state_dict = trainer.ema_state_dict
 
 
 def _frozen(net):
@@ -349,12 +394,16 @@ class Trainer:
 
     checkpoint_tag = "G"                          # glare_amd.fit: <out>/models/<iter>_G.pth
     perceptual, perceptual_weight = None, 1.0     # the frozen loss network of an objective with a perceptual term, and its factor
+    weights_ema = None                            # the decay of the averaged weights (FlatAdam), None: no average is kept
 
-    def __init__(self, netG, packed, precision, params, lr, weight_decay, **adam):
-        """packed: the parameters whose packed filters live across steps; params, lr, weight_decay, **adam: two_group_adam's."""
+    def __init__(self, netG, packed, precision, params, lr, weight_decay, weights_ema=None, **adam):
+        """packed: the parameters whose packed filters live across steps; params, lr, weight_decay, **adam: two_group_adam's.
+        weights_ema: a decay in [0, 1) keeps an exponential moving average of the trained weights (FlatAdam); a checkpoint then has a
+        second network file <iter>_<checkpoint_tag>_ema.pth (ema_state_dict), and ema_weights() runs anything under the average."""
         assert precision in ("bf16", "fp16")
         self.precision, self.netG, self.last_terms = precision, netG, {}
-        self.opt = two_group_adam(params, lr, weight_decay, precision=precision, **adam)
+        self.opt = two_group_adam(params, lr, weight_decay, precision=precision, weights_ema=weights_ema, **adam)
+        self.weights_ema = self.opt.weights_ema
         self.pack_cache = ops.PackCache(packed)
 
     def step_tensor(self, gt_img, lr_img=None, branch=None):
@@ -368,12 +417,78 @@ class Trainer:
 
     # ---- what the training driver asks (glare_amd.fit) ----
     def extra_networks(self):
-        """{suffix: module}: further networks of a checkpoint, written as <iter>_<suffix>.pth beside <iter>_<checkpoint_tag>.pth."""
-        return {}
+        """{suffix: module}: further networks of a checkpoint, written as <iter>_<suffix>.pth beside <iter>_<checkpoint_tag>.pth.  With
+        weights_ema: <iter>_<checkpoint_tag>_ema.pth, the averaged weights under the network's own key names (the suffix ends in `_ema`, so
+        glare_amd.evaluate's `*_<tag>.pth` glob does not take it for a checkpoint of its own)."""
+        return {} if self.weights_ema is None else {self.checkpoint_tag + EMA_SUFFIX: _AveragedNetwork(self)}
 
     def extra_state(self):
         """Further top-level entries of a `.state` file (the reference's resume reads its five keys by name and ignores any other)."""
-        return {}
+        return {} if self.weights_ema is None else {WEIGHTS_EMA_KEY: {"decay": self.weights_ema}}
+
+    # ---- the averaged weights (weights_ema) ----
+    def _averaged_params(self):
+        """[(parameter, its slice of the group's `ema`)] over the parameters Adam updates.  A parameter declared
+        never_used is not listed: it never moves by Adam, and what else writes it (the EMA codebook of stage 1) is taken live."""
+        out = []
+        for g in self.opt.groups:
+            off = 0
+            for p, used in zip(g.params, g.has_grad):
+                k = p.numel()
+                if used and k:
+                    out.append((p, g.ema[off:off + k]))
+                off += k
+        return out
+
+    def ema_seeded(self):
+        """Has a step seeded the average (or a resume loaded it)?  A host read."""
+        return self.weights_ema is not None and bool(int(self.opt.ema_seeded.item()))
+
+    def ema_state_dict(self):
+        """netG.state_dict() with every trained parameter's tensor replaced by its average; buffers, frozen and never-used parameters are
+        the live ones.  Before the first step there is no average yet: the live weights."""
+        sd = self.netG.state_dict()
+        if not self.ema_seeded():
+            return sd
+        avg = {p.data_ptr(): e.view(p.shape) for p, e in self._averaged_params()}
+        return type(sd)((k, avg[v.data_ptr()] if v.data_ptr() in avg and v.shape == avg[v.data_ptr()].shape else v) for k, v in sd.items())
+
+    def load_ema_weights(self, path):
+        """The resume side of <iter>_<checkpoint_tag>_ema.pth: the file's tensors into the `ema` buffers (whatever it does not name
+        starts from the live weights) and the flag set.  A missing file is refused by name."""
+        assert self.weights_ema is not None, "load_ema_weights: the trainer was built without weights_ema"
+        if not os.path.exists(path):
+            raise ValueError(EMA_RESUME_REFUSAL % path)
+        sd = torch.load(path, map_location="cpu")
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+        names = {p.data_ptr(): k for k, p in self.netG.named_parameters()}
+        for g in self.opt.groups:
+            if g.w.numel():
+                g.ema.copy_(g.w)
+        for p, e in self._averaged_params():
+            name = names.get(p.data_ptr())
+            if name in sd:
+                e.copy_(sd[name].reshape(-1).to(e.device, torch.float32))
+        self.opt.ema_seeded.fill_(1)
+
+    def _swap_averaged(self):
+        for g in self.opt.groups:
+            if g.w.numel():
+                for lo, hi in g.active_ranges():       # what Adam updates; the rest stays live, as in ema_state_dict()
+                    T.swap_(g.w[lo:hi], g.ema[lo:hi])
+        self.invalidate()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with trainer.ema_weights():` -- the network holds the averaged weights inside (w and ema exchanged in place, no third buffer;
+        packed inference weights dropped on the way in and out) and the live ones, bit for bit, after.  No training step inside."""
+        if not self.ema_seeded():
+            raise RuntimeError(EMA_UNSEEDED_REFUSAL)
+        self._swap_averaged()
+        try:
+            yield self
+        finally:
+            self._swap_averaged()
 
     def load_extra_state(self, state):
         """The resume side of extra_state(): `state` is the whole `.state` dict."""
@@ -412,7 +527,8 @@ class Stage2Trainer(Trainer):
     """One optimisation step of the flow objective: a7 (frozen VQGAN encoder, no tape) -> a1 -> a4 -> mean NLL -> backward ->
     gradient mean over ranks -> Adam."""
 
-    def __init__(self, netG, net_hq, lr_G=5e-4, lr_RRDB=None, weight_decay_G=0.0, train_rrdb=True, device_state=False, precision="fp16"):
+    def __init__(self, netG, net_hq, lr_G=5e-4, lr_RRDB=None, weight_decay_G=0.0, train_rrdb=True, device_state=False, precision="fp16",
+                 weights_ema=None):
         self.net_hq = _frozen(net_hq)
         rrdb = [p for n, p in netG.named_parameters() if n.startswith("RRDB.")]
         other = [p for n, p in netG.named_parameters() if not n.startswith("RRDB.")]
@@ -421,7 +537,7 @@ class Stage2Trainer(Trainer):
                 p.requires_grad_(False)
         never = [p for n, p in netG.named_parameters() if n.startswith(STAGE2_NEVER_USED)]
         super().__init__(netG.train(), [p for p in netG.parameters() if p.requires_grad], precision, other, lr_G, weight_decay_G,
-                         never_used=never, second=rrdb if train_rrdb else [], second_lr=lr_RRDB, second_weight_decay=1e-5)
+                         never_used=never, second=rrdb if train_rrdb else [], second_lr=lr_RRDB, second_weight_decay=1e-5, weights_ema=weights_ema)
 
     def graph_branches(self):
         """mean = color_map, and mean = gt where it can be drawn (train_gt_ratio > 0: 0.2 in confs/train_stage2_LOL.yml, 0 in LOL.yml)."""
@@ -468,7 +584,7 @@ class Stage3Trainer(Trainer):
     reference downloads torchvision's pretrained VGG16, which is not available offline; pass None to train on L1 + MS-SSIM."""
 
     def __init__(self, netG, net_hq, lr_G=5e-5, weight_decay_G=0.0, perceptual=None, use_msssim=True, device_state=False, precision="fp16",
-                 frozen_fp32_class=False):
+                 frozen_fp32_class=False, weights_ema=None):
         """frozen_fp32_class: run the FROZEN conditional encoder + flow in the fp32-class inference form (hi / lo operand pairs, three
         MFMA passes per conv) instead of the single-pass fp16 form.  Default False: the reference runs these nets under `@autocast()`
         in the stage-3 step (VQLLFLOWDeformable_arch.py:222-248), i.e. single-pass fp16 is ITS arithmetic; the fp32-class form serves
@@ -479,7 +595,7 @@ class Stage3Trainer(Trainer):
             p.requires_grad_(n.startswith("deformable_decoder."))
         dd = [p for n, p in netG.named_parameters() if n.startswith("deformable_decoder.")]
         never = [p for n, p in netG.named_parameters() if n.startswith(STAGE3_NEVER_USED)]
-        super().__init__(netG, dd, precision, dd, lr_G, weight_decay_G, never_used=never, second_weight_decay=1e-5)
+        super().__init__(netG, dd, precision, dd, lr_G, weight_decay_G, never_used=never, second_weight_decay=1e-5, weights_ema=weights_ema)
 
     def invalidate(self):
         """Only the deformable decoder's packed inference weights go stale; the frozen nets keep theirs."""
@@ -531,7 +647,7 @@ class Stage1Trainer(Trainer):
     def __init__(self, net, lr_G=1e-4, weight_decay_G=0.0, codebook_weight=1.0, perceptual=None, perceptual_weight=1.0,
                  device_state=False, precision="fp16", discriminator=None, disc_start=10000, disc_weight=0.8, disc_factor=1.0,
                  codebook_usage=False, codebook_restart=0, restart_threshold=0, codebook_ema=None, ema_eps=1e-5, semantic=None,
-                 semantic_weight=0.1):
+                 semantic_weight=0.1, weights_ema=None):
         """lr_G: a starting point, not a tuned value (the reference sets `self.learning_rate` from a config it does not ship).
         discriminator: an NLayerDiscriminator on the net's device, or None (no GAN term: the step and every file are what they were);
         disc_start / disc_weight / disc_factor: taming's defaults for the VQGAN configs.
@@ -575,7 +691,9 @@ class Stage1Trainer(Trainer):
         branch is dead there (its forward passes no vgg_feat); the ancestor optimises all of net_g.  The term's gradient reaches the
         encoder and quant_conv through the straight-through output and never a codebook row, so it goes together with codebook_ema,
         codebook_restart, the discriminator and LPIPS.  The loss network is in no checkpoint: objective_tag() names it with its weight, and
-        a resume under another objective is refused."""
+        a resume under another objective is refused.
+        weights_ema: Trainer's.  The generator alone is averaged: the discriminator's optimizer gets no average.  Under codebook_ema the
+        codebook is outside what Adam updates, so it is not averaged either: <iter>_VQ_ema.pth and ema_weights() carry the live one."""
         self.semantic, self.semantic_weight = semantic, float(semantic_weight)
         self.codebook_usage = bool(codebook_usage)
         self.codebook_ema, self.ema_eps = (None if codebook_ema is None else float(codebook_ema)), float(ema_eps)
@@ -592,7 +710,7 @@ class Stage1Trainer(Trainer):
         if self.codebook_ema is not None:            # in the flat layout as ever (one `.state` layout), outside what Adam updates
             never.append(E)
         super().__init__(net.train(), [p for n, p in named if not n.startswith(STAGE1_NEVER_USED)], precision, [p for _, p in named], lr_G,
-                         weight_decay_G, never_used=never, betas=(0.5, 0.9))
+                         weight_decay_G, never_used=never, betas=(0.5, 0.9), weights_ema=weights_ema)
         self.net = self.netG                         # `netG`: the name the driver and the checkpoint code read
         if semantic is not None:
             net.semantic_weight = self.semantic_weight
@@ -628,12 +746,12 @@ class Stage1Trainer(Trainer):
 
     def extra_networks(self):
         """<iter>_D.pth: taming's NLayerDiscriminator state dict."""
-        return {} if self.discriminator is None else {"D": self.discriminator}
+        return dict(super().extra_networks(), **({} if self.discriminator is None else {"D": self.discriminator}))
 
     def extra_state(self):
         """D's Adam and GradScaler state, the restart's window with its two settings, and the EMA's two tensors with theirs, travel as
         further keys of the `.state` file."""
-        extra = {}
+        extra = super().extra_state()
         if self.discriminator is not None:
             extra[DISC_KEY] = {"optimizer": checkpoint.adam_state_dict(self.opt_d), "scaler": self.opt_d.scaler_state_dict()}
         if self.codebook_restart:
@@ -884,6 +1002,7 @@ class GraphedStep:
         opt = self.trainer.opt
         snap = [(t, t.clone()) for g in opt.groups for t in (g.w, g.m, g.v)]
         snap += [(t, t.clone()) for t in (opt.step_dev, opt.state3, opt.scale, opt.growth_tracker)]
+        snap += [(t, t.clone()) for t in opt.ema_tensors()]      # the warm-up steps must neither seed nor advance the weight average
         actnorms = [m for m in self.trainer.netG.modules() if hasattr(m, "inited") and hasattr(m, "logs")]
         # "fresh" as FlowActNorms.py:36-38 defines it: not yet initialised AND still all-zero (a seeded / loaded ActNorm is only marked)
         fresh = {id(m) for m in actnorms if not m.inited and not bool((m.bias != 0).any())}

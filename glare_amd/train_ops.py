@@ -552,6 +552,26 @@ def gradscaler_update_(scale, tracker, found, growth_factor=2.0, backoff_factor=
                                              stream_handle()), "glare_gradscaler_update")
 
 
+def weight_ema_(ema, w, decay, seeded):
+    """ema = w where seeded (int32 [1], device) is 0, else ema = fmaf(decay, ema, (1 - decay) * w), in place (csrc/weight_ema.hip;
+    BaseModel.model_ema).  `decay` is taken as its fp32 value d; 1 - d is formed in fp64 from THAT value and rounded to fp32 once.  The
+    flag is only read: the caller fills it after the last buffer of a step."""
+    require_cuda(ema, w, seeded)
+    assert ema.dtype == w.dtype == torch.float32 and ema.is_contiguous() and w.is_contiguous() and ema.numel() == w.numel()
+    assert seeded.dtype == torch.int32 and seeded.numel() == 1 and ema.device == w.device == seeded.device
+    d = host_f32([decay])[0]                      # the C `float` the kernel receives
+    check(_lib.lib().glare_weight_ema_f32(ptr(ema), ptr(w), ema.numel(), d, 1.0 - d, ptr(seeded), stream_handle()), "glare_weight_ema_f32")
+    return ema
+
+
+def swap_(a, b):
+    """a <-> b in place: two fp32 buffers of one size that do not overlap (csrc/weight_ema.hip)."""
+    require_cuda(a, b)
+    assert a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
+    assert a.device == b.device
+    check(_lib.lib().glare_swap_f32(ptr(a), ptr(b), a.numel(), stream_handle()), "glare_swap_f32")
+
+
 def actnorm_init_(x, C, bias, logs, off=0, scale=1.0):
     """ActNorm's data-dependent initialisation (FlowActNorms.py:32-46) from x fp32 [..., pitch] (channels [off, off + C)):
     writes bias / logs (fp32, C elements, any shape) in place."""

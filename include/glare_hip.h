@@ -1068,6 +1068,23 @@ int glare_vq_semantic_bf16(const float* quant, const float* weight, const float*
 int glare_vq_semantic_scale_f32(const float* g_dev, long long n_tokens, const float* dq_unit, const float* dW_unit, const float* db_unit,
                                 float* dq, float* dW, float* db, glare_stream_t stream);
 
+/* ---- an exponential moving average of the trained weights (csrc/weight_ema.hip) ---------------------------------------------------
+ * Replaces BaseModel.model_ema of the reference's stage-1 lineage (basicsr/models/base_model.py:85-92: `net_g_ema = decay * net_g_ema +
+ * (1 - decay) * net_g`, one torch op per parameter) with one streaming launch over a flat fp32 parameter buffer, in place on `ema`:
+ *   *seeded_device == 0:  ema[i] = w[i]                                              (a bit copy: the first step seeds the average)
+ *   otherwise:            ema[i] = fmaf(decay, ema[i], one_minus_decay * w[i])       (one rounded product, one rounded fma)
+ * The caller passes one_minus_decay = (float)(1.0 - (double)decay).  *seeded_device (int32) is read, never written: the caller sets it with
+ * a device-side fill after the last buffer of a step, so a captured step holds the same launches on its first and on every later replay.
+ * fp32 only; both pointers need 4-byte alignment alone (16-byte vector accesses where they allow, single elements at the edges); the two
+ * ranges must not overlap.  GLARE_ERR_INVALID: n < 0, decay outside [0, 1) or NaN, and with n > 0 a null or misaligned pointer;
+ * n == 0 is a no-op that returns GLARE_OK.
+ * glare_swap_f32 exchanges two fp32 buffers of n elements in place, with the same alignment handling (validation under the averaged weights
+ * without a third buffer: swap, score, swap back).  GLARE_ERR_INVALID: n < 0, and with n > 0 a null or misaligned pointer or ranges that
+ * overlap. */
+int glare_weight_ema_f32(float* ema, const float* w, long long n, float decay, float one_minus_decay, const int* seeded_device,
+                         glare_stream_t stream);
+int glare_swap_f32(float* a, float* b, long long n, glare_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
