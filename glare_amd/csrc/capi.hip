@@ -1,7 +1,8 @@
 // Version / status entry points of libglare_hip.so.
 #include "common.h"
 
-extern "C" int glare_version(void) { return 130; }  // 1.30: + averaged weights (glare_weight_ema_f32, glare_swap_f32)
+extern "C" int glare_version(void) { return 131; }  // 1.31: + NIQE of unpaired results (glare_niqe_luma_u8, _mscn_f32, _block_moments_f32, _halve_f32)
+                                                    // 1.30: + averaged weights (glare_weight_ema_f32, glare_swap_f32)
                                                     // 1.29: + semantic guidance (glare_vq_semantic_bf16, glare_vq_semantic_scale_f32)
                                                     // 1.28: + EMA codebook (glare_vq_ema_stats_f32, glare_vq_ema_update_f32, glare_vq_restart_ema_f32)
                                                     // 1.27: + codebook restart (glare_vq_restart_f32)

@@ -2,7 +2,7 @@
 code/infer_unpaired.py:91-136 on the HIP path.
 
     python -m glare_amd.enhance photos/ more/img.png --out enhanced/ [--net-g G.pth --net-vq VQ.pth --precision fp16 --batch 8]
-                                [--tile 512 --tile-overlap 64]
+                                [--tile 512 --tile-overlap 64] [--niqe niqe_pris_params.npz]
 
 Per image, the reference's steps: read as RGB uint8 (cv2.imread, :47), auto_padding to a multiple of 16 with cv2.BORDER_REFLECT
 (:81-88), /255, log(clamp(x + 1e-3, min=1e-3)) (:39, :122), the network (get_sr, :128), crop + clamp + rgb() -- which truncates
@@ -340,10 +340,14 @@ def load_nets(net_g=None, net_vq=None, device=None):
 
 
 def run(inputs, out_dir, netG=None, net_vq=None, precision=None, batch=8, enhance_fn=None, device=None, tile=None, overlap=64,
-        tile_fn=None, blend_fn=None):
+        tile_fn=None, blend_fn=None, niqe=None, niqe_fn=None):
     """Enhance every readable image of `inputs` (files and folders) into out_dir under its basename; -> the result dict of the
     JSON line (per-image name / size / padded size, "tiles": [n_ty, n_tx] for an image enhanced in tiles, skipped files with reasons,
-    bf16 re-runs, seconds, images/s, MP/s).  tile / overlap: as enhance_images."""
+    bf16 re-runs, seconds, images/s, MP/s).  tile / overlap: as enhance_images.
+    niqe: a NIQE pristine model (metrics.load_niqe_params).  Every image entry then gains "niqe_in" (the input) and "niqe" (the enhanced
+    image, assembled where it was tiled) -- null with a "niqe_reason" where an image has no score -- and the line "niqe_in_mean",
+    "niqe_mean" (over the scored images) and "niqe_seconds"; scoring runs after the timed region, which stays what it is without it.
+    niqe_fn(list of uint8 images) -> list of (score or None, reason or None) replaces metrics.niqe_scores."""
     files = list_inputs(inputs)
     imgs, names, skipped = [], [], []
     for f in files:
@@ -371,12 +375,28 @@ def run(inputs, out_dir, netG=None, net_vq=None, precision=None, batch=8, enhanc
         write_image(os.path.join(out_dir, nm), o)
     mp = sum(a.shape[0] * a.shape[1] for a in imgs) / 1e6
     tiles = report.get("tiles", {})
-    return {"images": [dict({"name": n, "size": [int(a.shape[0]), int(a.shape[1])], "padded": p}, **({"tiles": tiles[n]} if n in tiles else {}))
+    res = {"images": [dict({"name": n, "size": [int(a.shape[0]), int(a.shape[1])], "padded": p}, **({"tiles": tiles[n]} if n in tiles else {}))
                        for n, a, p in zip(names, imgs, report.get("padded", []))],
             "skipped": skipped, "bf16_rerun_images": report.get("bf16_rerun_images", []),
             "seconds": round(secs, 4), "seconds_per_image_by_size": report.get("seconds_per_image_by_size", {}), "images_per_sec": round(len(imgs) / secs, 3) if imgs and secs > 0 else 0.0,
             "megapixels_per_sec": round(mp / secs, 3) if imgs and secs > 0 else 0.0,
             "timed": "uint8 in pinned host memory -> uint8 back on the host, one warm-up image first; file decode / encode excluded"}
+    if niqe is not None:
+        if niqe_fn is None:
+            from . import metrics
+
+            niqe_fn = lambda ims: metrics.niqe_scores(ims, niqe)
+        t1 = time.perf_counter()
+        scored = {"niqe_in": niqe_fn(imgs), "niqe": niqe_fn(outs)}       # each ends in a copy to the host: synchronous
+        res["niqe_seconds"] = round(time.perf_counter() - t1, 4)
+        for key, pairs in scored.items():
+            for entry, (score, why) in zip(res["images"], pairs):
+                entry[key] = score
+                if score is None:
+                    entry.setdefault("niqe_reason", why)
+            vals = [s for s, _ in pairs if s is not None]
+            res[key + "_mean"] = sum(vals) / len(vals) if vals else None
+    return res
 
 
 def main(argv=None):
@@ -392,13 +412,23 @@ def main(argv=None):
                     help="enhance an image with a side longer than N pixels as overlapping N x N tiles that are feathered together (a multiple of 16, "
                          "e.g. 512); without it such an image must fit the kernels' size envelope (about 4 MP)")
     ap.add_argument("--tile-overlap", type=int, default=64, metavar="O", help="overlap of neighbouring tiles in pixels (>= 16, at most N / 2)")
+    ap.add_argument("--niqe", default=None, metavar="PARAMS.npz",
+                    help="score every input and every enhanced image with NIQE on the device (lower is better); PARAMS.npz is the pristine "
+                         "model, basicsr's niqe_pris_params.npz")
     args = ap.parse_args(argv)
     import torch
+
+    niqe = None
+    if args.niqe is not None:
+        from . import metrics
+
+        niqe = metrics.load_niqe_params(args.niqe)          # a bad file is refused before the networks are built
 
     assert torch.cuda.is_available(), "glare_amd.enhance needs an MI355X: the HIP kernels are the only implementation"
     device = torch.device("cuda", torch.cuda.current_device())
     netG, net_vq = load_nets(args.net_g, args.net_vq, device)
-    res = run(args.inputs, args.out, netG, net_vq, args.precision, max(1, args.batch), device=device, tile=args.tile, overlap=args.tile_overlap)
+    res = run(args.inputs, args.out, netG, net_vq, args.precision, max(1, args.batch), device=device, tile=args.tile, overlap=args.tile_overlap,
+              niqe=niqe)
     print(json.dumps(res))
     return res
 

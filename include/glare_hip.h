@@ -1085,6 +1085,37 @@ int glare_weight_ema_f32(float* ema, const float* w, long long n, float decay, f
                          glare_stream_t stream);
 int glare_swap_f32(float* a, float* b, long long n, glare_stream_t stream);
 
+/* ---- NIQE of unpaired results (csrc/niqe.hip; glare_amd.metrics.niqe) ---------------------------------------------------------------
+ * The device part of the no-reference score the paper reports on MEF / LIME / DICM / NPE / VV (Mittal et al., "Making a 'Completely
+ * Blind' Image Quality Analyzer", 2013, as basicsr's calculate_niqe evaluates it; driver: basicsr/metrics/calculate_niqe.py).  The host
+ * turns the block moments into the 36 features per block and the score (fp64).  All four are fp32 streaming kernels that launch on
+ * `stream`, write only caller-owned buffers, need no workspace, use no atomics and sum in one fixed order: the same bits on every run.
+ * GLARE_ERR_INVALID: a null pointer, a non-positive size, a shape the entry refuses below; GLARE_ERR_UNSUPPORTED: B > 65535 or a size
+ * past a 31-bit index, named below -- all before any launch.
+ * glare_niqe_luma_u8: uint8 RGB HWC [B][h][w][3] -> y fp32 [B][H][W], H = 96 (h / 96), W = 96 (w / 96): the top-left crop to whole
+ *   96 x 96 blocks of y = 16 + round((65481 R + 128553 G + 24966 B) / 255000), ties to even, in integer arithmetic (BT.601 luma,
+ *   basicsr's rgb2ycbcr(y_only) and round()).  h < 96 or w < 96 is GLARE_ERR_INVALID (nothing to write); y_out 16-byte aligned.
+ * glare_niqe_mscn_f32: y [B][H][W] -> n = (y - mu) / (sigma + 1), mu = window (*) y, sigma = sqrt|window (*) y^2 - mu^2|; (*) is a
+ *   true convolution with the 7 x 7 window_host (49 host floats, row-major; the kernel flips it) over a replicated border
+ *   (scipy.ndimage.convolve, mode = 'nearest').  Evaluated about the centre pixel c: d = y - c, S1 = sum w d, S2 = sum w d^2,
+ *   y - mu = c one_minus_s0 - S1, var = S2 - S1^2 + one_minus_s0 (c^2 s0 + 2 c S1) -- equal in real numbers, without the cancellation of
+ *   E[y^2] - mu^2.  s0 = (float) sum(window), one_minus_s0 = (float)(1 - sum(window)), both taken by the caller in fp64.
+ * glare_niqe_block_moments_f32: n [B][H][W], bh | H, bw | W, bh bw <= GLARE_NIQE_MAX_BLOCK (else GLARE_ERR_UNSUPPORTED) -> out fp64
+ *   [B][W / bw][H / bh][5][5]: blocks column-major, as basicsr enumerates them; per block the five maps v = block, and block times
+ *   np.roll(block, (dy, dx), axis = (0, 1)) inside the block for (dy, dx) = (0, 1), (1, 0), (1, 1), (1, -1); per map
+ *   { count(v < 0), count(v > 0), sum_{v<0} v^2, sum_{v>0} v^2, sum |v| }.  One workgroup per block, the block held in LDS; products,
+ *   squares and sums in fp64.
+ * glare_niqe_halve_f32: y [B][H][W] -> [B][H / 2][W / 2], MATLAB's antialiased bicubic imresize(., 0.5) for even sizes: the separable
+ *   taps {-3, -9, 29, 111, 111, 29, -9, -3} / 256 over inputs 2 j - 3 .. 2 j + 4, the H pass and then the W pass, each rounded to fp32,
+ *   edges reflected including the edge pixel.  H, W even and >= 4, anything else GLARE_ERR_INVALID. */
+#define GLARE_NIQE_BLOCK 96
+#define GLARE_NIQE_MAX_BLOCK 9216
+int glare_niqe_luma_u8(const unsigned char* img_hwc, int B, int h, int w, float* y_out, glare_stream_t stream);
+int glare_niqe_mscn_f32(const float* y, int B, int H, int W, const float* window_host, float s0, float one_minus_s0, float* n_out,
+                        glare_stream_t stream);
+int glare_niqe_block_moments_f32(const float* n, int B, int H, int W, int bh, int bw, double* out, glare_stream_t stream);
+int glare_niqe_halve_f32(const float* y, int B, int H, int W, float* out, glare_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
