@@ -69,7 +69,8 @@ __global__ __launch_bounds__(256) void conv_direct_f32_kernel(const float* __res
     const int co = co0 + cg * MC_COT + e;
     if (co < Cout) {
       float v = acc[e] + (bias ? bias[co] : 0.f);
-      if (relu) v = fmaxf(v, 0.f);
+      if (relu && v <= 0.f) v = 0.f;      // torch.relu: a NaN stays a NaN -- fmaxf(NaN, 0) = 0 would hide a broken image behind a finite
+                                          // LPIPS (harness.hip's clamp says the same of PSNR); every other value keeps its bits
       out[((size_t)b * Cout + co) * OH * OW + p] = v;
     }
   }
@@ -85,7 +86,10 @@ __global__ __launch_bounds__(256) void maxpool_f32_kernel(const float* __restric
     const float* xp = x + pl * H * W + (size_t)(oy * stride) * W + ox * stride;
     float m = xp[0];
     for (int ky = 0; ky < k; ++ky)
-      for (int kx = 0; kx < k; ++kx) m = fmaxf(m, xp[ky * W + kx]);
+      for (int kx = 0; kx < k; ++kx) {
+        const float v = xp[ky * W + kx];
+        m = (v > m || v != v) ? v : m;      // max_pool2d propagates a NaN (fmaxf drops it): once m is a NaN no comparison replaces it
+      }
     out[i] = m;
   }
 }

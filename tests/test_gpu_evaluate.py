@@ -10,30 +10,13 @@ from glare_amd import modules as M
 from glare_amd.fit import default_options
 from glare_amd.modules._base import to_nchw
 from glare_amd.synthetic import seeded_init_, synthetic_gt, synthetic_lowlight
+from scoring_fp64 import output_and_gt as _output          # the generator, shared with test_gpu_scoring_edges.py
 
 pytestmark = pytest.mark.gpu
 
 # (B, Hp, Wp, window): odd sizes -- rows that start at any byte of a 4-byte word, tail lanes, words that straddle two images
 # (3 * 29 * 41 = 3567 bytes per image); and one image smaller than a workgroup
 _SHAPES = [(3, 37, 53, (2, 5, 29, 41)), (1, 9, 11, (1, 2, 5, 7))]
-
-
-def _output(B, Hp, Wp, special=True):
-    """fp32 [B,3,Hp,Wp] below 0, above 1, on k/255 and one ulp either side; special: NaN, +inf and -inf sprinkled in."""
-    g = torch.Generator().manual_seed(Hp * Wp + B)
-    x = torch.rand(B, 3, Hp, Wp, generator=g, dtype=torch.float64).mul(1.4).sub(0.2).float()
-    k = torch.randint(0, 256, x.shape, generator=g).float() / 255
-    sel = torch.rand(x.shape, generator=g)
-    x = torch.where(sel < 0.3, k, x)
-    x = torch.where((sel >= 0.3) & (sel < 0.4), torch.nextafter(k, torch.tensor(2.0)), x)
-    x = torch.where((sel >= 0.4) & (sel < 0.5), torch.nextafter(k, torch.tensor(-1.0)), x)
-    if special:
-        flat = x.view(-1)
-        spec = torch.randint(0, flat.numel(), (max(6, flat.numel() // 50),), generator=g)
-        for j, i in enumerate(spec.tolist()):
-            flat[i] = (float("nan"), float("inf"), float("-inf"))[j % 3]
-    gt = torch.randint(0, 256, (B, Hp, Wp, 3), generator=g, dtype=torch.uint8)
-    return x, gt
 
 
 @pytest.mark.parametrize("B,Hp,Wp,window", _SHAPES)
